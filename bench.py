@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — JPerceiver `Baseline` train-step throughput on N MI355X of one node.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +12,9 @@ deterministic global norm, clip 35 + Adam).  Workload at every N (weak scaling):
 cfg_kitti_baseline_odometry_boundary_ce_iou_1024_20 — 1024x1024 (the size every reference config uses),
 frames [0,-1,1], type static, loss_sum 3, occ 256, fp32, 8 images per GPU.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step, ...).
+A plain run sets up, warms up, times the K steps and prints it; the objects below are null there.  --full adds them (each
+can still be left out with its --no-* option):
   roofline     — the BY-TIME DOMINANT kernel of one instrumented step: every implicit-GEMM dispatch is bracketed by HIP
                  events inside the library, on the stream it is launched on (jp_profile_*); dominant = the kernel
                  instantiation with the largest summed duration.
@@ -21,12 +23,15 @@ Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
                  -DJP_NS=3 build; the dense 16-bit MFMA peak is the same for both), against 157.3 TFLOP/s for
                  the exact-fp32 MFMA kernels.  Step-level figures ride along: step_fp32_equiv_tflops = 1.63 TFLOP*B / t_step,
                  achieved_hbm = (9.7 GB*B + 2.3 GB) / t_step, and per-pipe aggregates of all igemm kernels.
-  families     — per-kernel-family time / rate table of that step (also written to $JP_BENCH_TABLE or
-                 gpurun_out/bench_families.json).
+  families     — per-kernel-family time / rate table of that step (the whole table is also written to the file named by
+                 $JP_BENCH_TABLE).
   cpu_baseline — the oracle (PyTorch-CPU port of the reference step) timed on this host's cores at B=1, SAME flags as
                  the GPU workload (static, 3 frames, loss_sum 3, 1024^2).
   secondary    — clearly labelled, NOT the headline: the shape-agnostic depth/pose/CGT/photometric sub-path at
                  BASELINE.json's 1024(W)x320(H) with the (square-only) layout branch disabled.
+  exact_build  — the same workload on the -DJP_NS=3 build of the library (exact_build_figure).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import collections
@@ -234,6 +239,47 @@ def timed_steps(runner, batch, steps, warmup, world, dev, log, calibrate=None, p
     return dt, out, multi
 
 
+DUMP_SAMPLE = 4 << 20      # elements kept of a flat vector longer than this (a fixed, seeded sample of its positions)
+
+
+def dump_outputs(path, runner, out, log):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy --
+      loss.npy                the summed loss (float64, shape (1,));
+      log_vars.<term>.npy     every logged loss term (float64, shape (1,));
+      params.npy / grads.npy  all parameters after the step's clip + Adam update and the step's gradients, flattened in
+                              state_dict order (float32); longer than DUMP_SAMPLE elements: the positions np.unique of
+                              default_rng(0).integers(0, n, DUMP_SAMPLE) -- the same positions for the same model;
+      buffers.npy             the BatchNorm running statistics, flattened in state_dict order (float32).
+    Inputs, weights and the step's random draws are seeded, so the same arguments give the same inputs in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    model = getattr(runner.model, "module", runner.model)
+    loss = out["loss"]
+    files = {"loss": np.array([float(loss.detach() if torch.is_tensor(loss) else loss)], dtype=np.float64)}
+    for k, v in out["log_vars"].items():
+        if k != "loss":       # ('min_reconstruct_loss', 0) -> log_vars.min_reconstruct_loss_0
+            files["log_vars." + re.sub(r"[^A-Za-z0-9.-]+", "_", str(k)).strip("_")] = np.array([float(v)], dtype=np.float64)
+    named = dict(model.named_parameters())
+    sd = model.state_dict()
+    pn = [n for n in sd if n in named]
+    bn = [n for n in sd if n not in named and sd[n].is_floating_point()]
+
+    def flat(ts, name):
+        v = torch.cat([t.detach().reshape(-1).float() for t in ts])
+        if v.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, v.numel(), DUMP_SAMPLE))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        files[name] = v.cpu().numpy().astype(np.float32)
+
+    flat([sd[n] for n in pn], "params")
+    flat([named[n].grad if named[n].grad is not None else torch.zeros_like(named[n]) for n in pn], "grads")
+    if bn:
+        flat([sd[n] for n in bn], "buffers")
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"--dump-outputs: {len(files)} arrays, {sum(a.nbytes for a in files.values()) / 1e6:.1f} MB -> {path}")
+
+
 def _free_port():
     import socket
     with socket.socket() as sk:
@@ -267,6 +313,12 @@ def main():
     ap.add_argument("--graph", choices=("auto", "on", "off"), default="auto",
                     help="replay the whole iteration from one captured hipGraph (apis.trainer.CapturedStep); auto = for "
                          "single-process runs with <= 2 images per GPU, time both issue modes in the warm-up and keep the faster")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline / family table, the secondary 1024x320 workload, the CPU "
+                         "baseline and the -DJP_NS=3 build (off: a plain run only times the headline workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss terms, parameters, gradients, BatchNorm buffers) "
+                         "to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
@@ -322,6 +374,8 @@ def main():
     ms = dt / args.steps * 1e3
     value = B * world * args.steps / dt
     log(f"{args.steps} timed steps: {ms:.1f} ms/step, {value:.2f} images/s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runner, out, log)
     if os.environ.get("JP_PMC_CALIB") and rank == 0:
         # known-byte streaming copy (4 B/lane loads and stores, the igemm gather's access width) so that the
         # FETCH_SIZE / WRITE_SIZE counters of a rocprofv3 --pmc pass can be calibrated (MI355X_MICROARCH.md §HBM)
@@ -332,7 +386,7 @@ def main():
         torch.cuda.synchronize()
         del a, b
     roof, fam, cpu, sec = None, None, None, None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # every rank runs the instrumented step (it contains the gradient all-reduce); rank 0 reports
         runner.step_graph = False          # the instrumented step is issued launch by launch (HIP events around each)
         roof, fam = measure_roofline(runner, batch, B, ms * 1e-3, rank)
@@ -341,13 +395,13 @@ def main():
         dist.barrier()
     del runner, batch
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_secondary and args.config == 1:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and args.config == 1:
         sec = secondary_figure(dev, B, log)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("timing the CPU baseline (oracle) ...")
         cpu = cpu_baseline(HW, cfg)
     exact = None
-    if rank == 0 and world == 1 and not args.no_exact_build and not os.environ.get("JP_LIB_PATH"):
+    if args.full and rank == 0 and world == 1 and not args.no_exact_build and not os.environ.get("JP_LIB_PATH"):
         exact = exact_build_figure(args, log)
     if rank == 0:
         line = {

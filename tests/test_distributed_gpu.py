@@ -131,7 +131,7 @@ def test_bench_two_rank_code_path_on_one_gpu():
     env = dict(os.environ, JP_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", JP_BENCH_PREWARM="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "1", "--hw", "256", "--no-cpu-baseline", "--no-secondary"]
+           "--batch", "1", "--hw", "256", "--full", "--no-cpu-baseline", "--no-secondary"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -194,6 +194,13 @@ def test_conv_at_bench_shape(label, case, k_fwd, k_dgrad, k_wgrad):
     close(y.t, yr, rtol=2e-4, msg="fwd")
     gy = rnd(*yr.shape, seed=4)
     y.g = gy.clone()
+    yr.backward(gy.cpu())
+    R = None
+    if "accumulate into dx" in label:
+        # a second consumer's gradient already sits in dx: seeded, of the gradient's own size (a dropped or doubled add shifts every
+        # element by about its own magnitude)
+        R = rnd(*x.shape, seed=5) * float(xr.grad.pow(2).mean().sqrt())
+        xv.g = R.clone()
     was = ops._WG_ON
     ops._WG_ON = False
     try:
@@ -202,17 +209,19 @@ def test_conv_at_bench_shape(label, case, k_fwd, k_dgrad, k_wgrad):
     finally:
         ops._WG_ON = was
     _expect(kt.names, k_dgrad + k_wgrad, label + " backward")
-    yr.backward(gy.cpu())
     if needs_dx:
-        close(xv.g, xr.grad, rtol=2e-4, msg="dgrad")
+        close(xv.g, xr.grad if R is None else xr.grad + R.cpu(), rtol=2e-4, msg="dgrad")
     close(wv.g, wr.grad, rtol=2e-4, msg="wgrad")
     if bias:
         close(bv.g, br.grad, rtol=2e-4, msg="bias grad")
 
 
-@pytest.mark.parametrize("N,H,W,Cr,Cx,Cout", [(8, 256, 256, 256, 256, 256),     # iconv1: cat(reduce1, up(x2), disp2) @256^2
-                                               (8, 128, 128, 256, 256, 256),     # iconv2 @128^2
-                                               (8, 64, 64, 256, 256, 256)])      # iconv3 @64^2
+ICONV_BENCH_CASES = [(8, 256, 256, 256, 256, 256),     # N, H, W, Cr, Cx, Cout -- iconv1: cat(reduce1, up(x2), disp2) @256^2
+                     (8, 128, 128, 256, 256, 256),     # iconv2 @128^2
+                     (8, 64, 64, 256, 256, 256)]       # iconv3 @64^2
+
+
+@pytest.mark.parametrize("N,H,W,Cr,Cx,Cout", ICONV_BENCH_CASES)
 def test_iconv_at_bench_shape(N, H, W, Cr, Cx, Cout):
     """iconv_k(cat(reduce_k, up2x(x_{k+1}), disp_{k+1})) -> 256, reflect + leaky (depth_decoder.py:76-77), the three largest
     convolutions of the step: P9U forward, per-source dgrad (P9 on the skip segment, parity-class on the upsampled one),

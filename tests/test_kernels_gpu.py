@@ -139,7 +139,7 @@ def test_conv2d_fwd_bwd(case):
         close(bv.g, br.grad, rtol=2e-4, msg="bias grad")
 
 
-@pytest.mark.parametrize("N,H,W,Cr,Cx,Cout", [
+FUSED_UPSAMPLE_CASES = [            # N, H, W, Cr, Cx, Cout
     (2, 12, 20, 40, 24, 32),      # generic gather (unaligned segments)
     (3, 128, 128, 64, 64, 160),   # upsample-aware parity-class forward + per-source dgrad (4 slots on the upsampled segment)
     (3, 128, 128, 32, 96, 40),    # ... 64x256 tile, 3 channel chunks in the upsampled segment
@@ -150,7 +150,10 @@ def test_conv2d_fwd_bwd(case):
     (2, 64, 96, 256, 128, 64),    # ... two 128-row tiles, 2 images
     (2, 64, 128, 64, 96, 256),    # P9U patch kernel forward: 2 skip stages + 3 upsampled stages + disparity stage, 2 M tiles
     (1, 128, 128, 32, 32, 128),   # P9U: one stage of each kind, tiles at every image border
-])
+]
+
+
+@pytest.mark.parametrize("N,H,W,Cr,Cx,Cout", FUSED_UPSAMPLE_CASES)
 def test_conv2d_fused_upsample_concat(N, H, W, Cr, Cx, Cout):
     """iconv_k(cat(reduce, up(x), disp)) and its three input gradients (depth_decoder.py:76-77)."""
     r, xh, d = rnd(N, Cr, H, W, seed=1), rnd(N, Cx, H // 2, W // 2, seed=2), rnd(N, 1, H, W, seed=3)
@@ -171,8 +174,11 @@ def test_conv2d_fused_upsample_concat(N, H, W, Cr, Cx, Cout):
         close(got, ref.grad, rtol=2e-4, msg=nm)
 
 
-@pytest.mark.parametrize("N,C,h,w", [(2, 40, 6, 10), (1, 256, 20, 36), (3, 64, 2, 2), (1, 256, 64, 64),
-                                     (8, 64, 128, 128)])      # large map: the one-chain two-pixel forward, precomputed-gather wgrad
+DISPARITY_HEAD_CASES = [(2, 40, 6, 10), (1, 256, 20, 36), (3, 64, 2, 2), (1, 256, 64, 64),      # N, C, h, w
+                        (8, 64, 128, 128)]      # large map: the one-chain two-pixel forward, precomputed-gather wgrad
+
+
+@pytest.mark.parametrize("N,C,h,w", DISPARITY_HEAD_CASES)
 def test_disparity_head_on_upsampled_source(N, C, h, w):
     """disp_k = sigmoid(Conv3x3_reflect(up2x(x))) (depth_decoder.py:36-39,70-71): upsample-aware direct kernels."""
     x = rnd(N, C, h, w, seed=1)
@@ -787,10 +793,13 @@ def test_act_bwd_bias_one_pass(N, C, H, W, act):
     close(db, (0.25 + ref.sum(dim=(0, 2, 3))).float(), rtol=1e-5, atol=1e-5, msg="dbias")
 
 
-@pytest.mark.parametrize("N,Cin,Cout,H,W,up,act,bias", [(2, 16, 16, 64, 128, 1, 0, False),    # BEV upconv 16 -> 16 on the upsampled map
-                                                        (3, 16, 16, 96, 128, 0, 1, True),      # full-resolution source, bias + ReLU, 3 images
-                                                        (1, 16, 16, 64, 64, 1, 2, True),
-                                                        (2, 32, 32, 64, 64, 1, 1, True)])      # (32 channels: implicit-GEMM engine)
+SMALL_CHANNEL_CASES = [(2, 16, 16, 64, 128, 1, 0, False),    # N, Cin, Cout, H, W, up, act, bias: BEV upconv 16 -> 16 on the upsampled map
+                       (3, 16, 16, 96, 128, 0, 1, True),      # full-resolution source, bias + ReLU, 3 images
+                       (1, 16, 16, 64, 64, 1, 2, True),
+                       (2, 32, 32, 64, 64, 1, 1, True)]       # (32 channels: implicit-GEMM engine)
+
+
+@pytest.mark.parametrize("N,Cin,Cout,H,W,up,act,bias", SMALL_CHANNEL_CASES)
 def test_small_channel_direct_conv(N, Cin, Cout, H, W, up, act, bias):
     """The 16 / 32-channel 3x3 zero-pad layers of the BEV decoder (layout_model.py:138-153) run on direct VALU kernels
     (conv_c16.hip): forward, input gradient (through the nearest-2x upsample where the source is stored at half resolution) and
@@ -870,11 +879,14 @@ print("RESULT", h, err, "|".join(names))
     assert out["1"][1] < 2e-5
 
 
-@pytest.mark.parametrize("N,C,H,W,expect", [(8, 64, 128, 128, True),      # ResNet layer1 shape class: 64-row 4-wave tiles (wide)
-                                            (8, 128, 64, 64, True),       # layer2: 128-row 4-wave tiles
-                                            (8, 64, 64, 96, True),        # regular (not wide) 64-row tiles
-                                            (8, 512, 32, 32, True),       # layer4: four 128-row M tiles per pixel tile (XCD-remapped ids)
-                                            (8, 256, 64, 128, False)])    # 256-row 8-wave tiles: no statistics epilogue -> the pass over y
+BN_EPILOGUE_CASES = [(8, 64, 128, 128, True),      # N, C, H, W, expect: ResNet layer1 shape class: 64-row 4-wave tiles (wide)
+                     (8, 128, 64, 64, True),       # layer2: 128-row 4-wave tiles
+                     (8, 64, 64, 96, True),        # regular (not wide) 64-row tiles
+                     (8, 512, 32, 32, True),       # layer4: four 128-row M tiles per pixel tile (XCD-remapped ids)
+                     (8, 256, 64, 128, False)]     # 256-row 8-wave tiles: no statistics epilogue -> the pass over y
+
+
+@pytest.mark.parametrize("N,C,H,W,expect", BN_EPILOGUE_CASES)
 def test_batchnorm_statistics_from_the_conv_epilogue(N, C, H, W, expect):
     """Round 6 (VERDICT r03-r05 "BatchNorm folded into the convolutions", resnet.py:29-45): a 3x3 convolution that feeds a train-mode
     BatchNorm leaves per-channel partial sums of y and y^2 in its epilogue (jp_conv2d_fwd* bn_stats) and jp_bn_train_fwd folds them

@@ -187,6 +187,39 @@ class Baseline(nn.Module):
         out["origin_features"] = F.t
         return out
 
+    # ------------------------------------------------------------------ eval-mode poses (net.py:630-642)
+    @torch.no_grad()
+    def predict_poses(self, inputs, frame_ids=None):
+        """The reference's `predict_poses` for an eval-mode model (its eval forward has the call commented out, net.py:76):
+        ("color_aug", f, 0) for f in `frame_ids` (default: the model's) -> ("cam_T_cam" | "axisangle" | "translation", 0, f)
+        for every f != 0.  Frames are resized to 192x640 and paired in temporal order ([f, 0] for f < 0, else [0, f]); the
+        transform is inverted for f < 0.  The ops of the training step's pose branch on the current stream, nothing recorded.
+        Without ("K", 0) an identity K is handed to jp_pose_fwd (only its K @ T by-product reads it)."""
+        if self.training:
+            raise RuntimeError("predict_poses expects an eval-mode model (call .eval(): BatchNorm must use running stats)")
+        frame_ids = list(self.opt.frame_ids if frame_ids is None else frame_ids)
+        ref = inputs[("color_aug", 0, 0)]
+        dev = ref.device
+        if dev.type != "cuda":
+            raise RuntimeError("Baseline runs on the GPU only: its kernels are HIP (no CPU fallback in the product path)")
+        ops.PackRegistry.of(dev).refresh_all()
+        B = ref.shape[0]
+        K = inputs.get(("K", 0))
+        K = torch.eye(4, device=dev).repeat(B, 1, 1) if K is None else K.contiguous()
+        out = {}
+        with recording(None):
+            pf = {f: ops.bilinear_resize(Var(inputs[("color_aug", f, 0)].contiguous()), 192, 640) for f in frame_ids}
+            for f in frame_ids:
+                if f == 0:
+                    continue
+                pair = [pf[f], pf[0]] if f < 0 else [pf[0], pf[f]]
+                at = self.PoseDecoder._fwd(self.PoseEncoder._fwd(ops.cat_channels(pair)))     # (B,6)
+                aa, tr = _split6(at)
+                out[("cam_T_cam", 0, f)] = ops_loss.pose(aa, tr, K, invert=(f < 0)).T
+                out[("axisangle", 0, f)] = aa.t.view(B, 1, 1, 3)
+                out[("translation", 0, f)] = tr.t.view(B, 1, 1, 3)
+        return out
+
     @staticmethod
     def _publish_head(out, sfx, tag, h):
         out["features" + sfx] = h["feats"].t

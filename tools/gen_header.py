@@ -105,6 +105,20 @@ GROUPS = [
      "of argmax(logits) vs label); depth compute_errors + median scaling + Garg crop mono/core/evaluation/pixel_error.py:27-40, "
      "mono/core/evaluation/eval_hooks.py:147-179.",
      ["jp_confusion2", "jp_depth_eval_prepare", "jp_masked_median", "jp_depth_errors"]),
+    ("Video perception post-processing (csrc/perception.hip; apis/perception.py) — what scripts/eval_kitti_video.py does in host numpy "
+     "on copied-back tensors.  jp_disp_resize_depth: disp_to_depth's scaled disparity 1/max_depth + (1/min_depth - 1/max_depth) disp, "
+     "half-pixel bilinear resize to OH x OW (cv2.resize INTER_LINEAR; the sampling rule of jp_bilinear_fwd) and 1/x in one pass "
+     "(:121-133); disp_out (nullable) receives the resized scaled disparity.  jp_quantiles: for every row of x (rows <= 64, n floats "
+     "each) and every q[i] (HOST array, nq <= 4, in [0,1]) the order statistics k = floor(q (n-1)) and min(k+1, n-1) into out "
+     "(rows, nq, 2) -- the two values numpy's `linear` quantile interpolates between (np.percentile :134; q = 0: the minimum); exact "
+     "radix selection on the order-preserving key of the float (4 passes of 8 bits, integer histograms: the result does not depend "
+     "on the launch order; np.sort's order: -0.0 == +0.0, +-Inf are values, NaN last); ws: jp_quantiles_ws_bytes(rows) bytes of "
+     "caller scratch, need not be initialised.  jp_colorize_u8: matplotlib Normalize + 256-entry colormap (plt.imsave(cmap, vmax) "
+     ":136) in fp32, idx = clamp((int)floorf((x - vmin) * (256.0f / (vmax - vmin))), 0, 255), 0 where vmax <= vmin, out = lut[idx]; "
+     "vmin_vmax (rows, 2) and lut (256 x 3 bytes) in device memory, out (rows, n, 3) bytes.  jp_layout_classes_u8: np.argmax of the "
+     "road and the car head (B, 2, HW; strictly-greater, ties -> 0; car_logits nullable) -> cls (B, HW) bytes 0 / 1 road / 2 car "
+     "and (nullable) rgb (B, HW, 3) with the palette (0,0,0) / (255,255,255) / (0,0,255) (:157-161,195-218).",
+     ["jp_disp_resize_depth", "jp_quantiles_ws_bytes", "jp_quantiles", "jp_colorize_u8", "jp_layout_classes_u8"]),
     ("Device-side input pipeline — MonoDataset.preprocess mono/datasets/mono_dataset.py:126-171 (PIL ANTIALIAS resize, bit-exact "
      "Pillow fixed-point resampler; ToTensor; ColorJitter in torchvision tensor arithmetic) and process_topview :417-431, applied "
      "to raw uint8 frames after one pinned async upload.",

@@ -12,6 +12,16 @@
         (the KITTI odometry text format written by the script).
     odometry(pose_encoder, pose_decoder, frames)
         both of the above over a sequence of frames: (n, 3, H, W) -> (n, 12).
+    chain_poses_device(T, invert=True)
+        chain_poses on the device: (n,4,4) float32 device transforms -> (n+1, 12) float64 device poses (jp_pose_chain_f64; the
+        general affine inverse, like np.linalg.inv; invert=False is eval_kitti_video.py:292's chaining).
+    odometry_device(pose_encoder, pose_decoder, frames, batch=8)
+        odometry() with the pairs run `batch` at a time and the chain on the device: (n,3,H,W) -> (n, 12) device float64.
+    evaluate_odometry(pose_encoder, pose_decoder, frames, gt_poses, batch=8, **eval_kw)
+        odometry_device + core.evaluation.eval_odometry (mono/tools/kitti_evaluation_toolkit.py: the paper's t_err / r_err).
+    read_kitti_poses(path) / write_kitti_poses(path, poses)
+        the KITTI pose text file: 12 numbers per line, or 13 with a leading frame index (loadPoses); written with '%1.8e'
+        like the script (draw_odometry.py:78).
 The networks must already hold a checkpoint (apis.load_checkpoint; the scripts copy `PoseEncoder.*` / `PoseDecoder.*`
 out of the training checkpoint's state dict, which `pose_nets_from_checkpoint` restates)."""
 from __future__ import annotations
@@ -19,7 +29,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .._lib import call
+from .._lib import call, lib
 from ..core import evaluation as ev
 
 
@@ -79,6 +89,75 @@ def odometry(pose_encoder, pose_decoder, frames) -> np.ndarray:
     """frames (n,3,H,W) CUDA tensor (already at the pose nets' resolution) -> (n, 12) chained poses."""
     Ts = [pose_between(pose_encoder, pose_decoder, frames[k:k + 1], frames[k + 1:k + 2])[0] for k in range(frames.shape[0] - 1)]
     return chain_poses(torch.stack(Ts)) if Ts else np.identity(4)[0:3].reshape(1, 12)
+
+
+def chain_poses_device(T, invert=True) -> torch.Tensor:
+    """(n,4,4) float32 device transforms -> (n+1, 12) float64 device poses: G_0 = I, G_k = G_{k-1} @ inv(T_k) (or @ T_k)."""
+    if not (isinstance(T, torch.Tensor) and T.is_cuda):
+        raise RuntimeError("chain_poses_device runs a HIP kernel: pass a CUDA tensor (chain_poses is the host version)")
+    if T.dim() != 3 or tuple(T.shape[1:]) != (4, 4) or T.dtype != torch.float32:
+        raise ValueError(f"expected (n,4,4) float32 transforms, got {tuple(T.shape)} {T.dtype}")
+    n = T.shape[0]
+    poses = torch.empty((n + 1, 12), device=T.device, dtype=torch.float64)
+    if n == 0:
+        poses[0] = torch.eye(4, device=T.device, dtype=torch.float64)[:3].reshape(12)
+        return poses
+    ws = torch.empty(lib().fn["jp_pose_chain_ws_bytes"](n), device=T.device, dtype=torch.uint8)
+    call("jp_pose_chain_f64", T.contiguous(), n, 1 if invert else 0, poses, ws)
+    return poses
+
+
+@torch.no_grad()
+def pair_transforms(pose_encoder, pose_decoder, frames, batch=8) -> torch.Tensor:
+    """frames (n,3,H,W) CUDA tensor -> (n-1,4,4) float32 device transforms of the pairs [frames[k] | frames[k+1]], `batch` pairs
+    per forward pass of the pose nets and per jp_pose_fwd launch."""
+    _eval(pose_encoder, pose_decoder)
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
+        raise RuntimeError("the pose nets run HIP kernels: pass frames as a CUDA tensor")
+    if int(batch) < 1:
+        raise ValueError("batch must be at least 1")
+    n = frames.shape[0] - 1
+    T = torch.empty((max(n, 0), 4, 4), device=frames.device)
+    for k0 in range(0, n, int(batch)):
+        k1 = min(n, k0 + int(batch))
+        B = k1 - k0
+        axisangle, translation = pose_decoder(pose_encoder(torch.cat([frames[k0:k1], frames[k0 + 1:k1 + 1]], 1).contiguous()))
+        aa, tr = axisangle[:, 0].reshape(-1, 3).contiguous(), translation[:, 0].reshape(-1, 3).contiguous()
+        K = torch.eye(4, device=aa.device).repeat(B, 1, 1)             # only T is used (P = K@T is a by-product)
+        P = torch.empty((B, 3, 4), device=aa.device)
+        call("jp_pose_fwd", aa, tr, K, T[k0:k1], P, B, 0)
+    return T
+
+
+@torch.no_grad()
+def odometry_device(pose_encoder, pose_decoder, frames, batch=8) -> torch.Tensor:
+    """odometry() without leaving the device: frames (n,3,H,W) -> (n, 12) float64 device poses."""
+    return chain_poses_device(pair_transforms(pose_encoder, pose_decoder, frames, batch), invert=True)
+
+
+def evaluate_odometry(pose_encoder, pose_decoder, frames, gt_poses, batch=8, **eval_kw):
+    """odometry_device + eval_odometry against gt_poses ((n,12) array or tensor, e.g. read_kitti_poses) -> eval_odometry's dict
+    plus `poses`, the predicted (n,12) device trajectory."""
+    pred = odometry_device(pose_encoder, pose_decoder, frames, batch)
+    gt = torch.as_tensor(np.asarray(gt_poses) if not isinstance(gt_poses, torch.Tensor) else gt_poses)
+    gt = gt.to(device=pred.device, dtype=torch.float64).reshape(-1, 12)
+    out = ev.eval_odometry(pred, gt, **eval_kw)
+    out["poses"] = pred
+    return out
+
+
+def read_kitti_poses(path) -> np.ndarray:
+    """KITTI pose file -> (n,12) float64; a 13-column file carries the frame index first (loadPoses), which is dropped."""
+    a = np.loadtxt(path, dtype=np.float64, ndmin=2)
+    if a.shape[1] not in (12, 13):
+        raise ValueError(f"{path}: expected 12 or 13 numbers per line, got {a.shape[1]}")
+    return np.ascontiguousarray(a[:, -12:])
+
+
+def write_kitti_poses(path, poses) -> None:
+    """(n,12) poses (array or tensor) -> text, one pose per line, '%1.8e' (draw_odometry.py:78)."""
+    p = poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else np.asarray(poses)
+    np.savetxt(path, np.asarray(p, dtype=np.float64).reshape(-1, 12), delimiter=" ", fmt="%1.8e")
 
 
 def pose_nets_from_checkpoint(checkpoint, pose_encoder, pose_decoder):

@@ -11,17 +11,29 @@ mono/core/evaluation/eval_hooks.py:147-199), computed by GPU reductions of libjp
                                         scaling (or the fixed x36 stereo scale), clamp, compute_errors -> dict incl. 'scale'
     disp_to_depth, AverageMeter         as in pixel_error.py
 
+and the KITTI odometry evaluation of mono/tools/kitti_evaluation_toolkit.py (`kittiOdomEval.eval`, the paper's t_err / r_err) with
+the alignment modes of scripts/plot_kitti.py, on (n,12) float64 device trajectories (csrc/odometry.hip):
+
+    umeyama_alignment(x, y, with_scale) (R, t, c) of Umeyama's least-squares similarity y ~ c R x + t (mono/tools/geometry.py:20-67):
+                                        the moments are one device reduction, the 3x3 SVD runs on the host on 19 numbers
+    align_poses(pred, gt, mode)         "umeyama_scale" (the toolkit's align_trajectory(correct_only_scale=True)), "scale",
+                                        "scale_7dof", "7dof", "6dof" (plot_kitti.py:223-243, both trajectories re-based to their
+                                        first pose), "none" -> (aligned trajectory, parameters)
+    eval_odometry(pred, gt)             align, then calcSequenceErrors' segment table (every `step` frames x every length of
+                                        100..800 m), computeOverallErr / computeSegmentErr / computeSpeedErr, plus the ATE
+
 Segmentation inputs are 2-class maps ({0, 1}; num_class = 2 in every north-star config).  The list-length quirks of the
 reference are kept: a class that occurs neither in the prediction nor in the label is simply absent from mean_IU's list.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 
 import numpy as np
 import torch
 
-from .._lib import call
+from .._lib import call, lib
 
 MIN_DEPTH = 1e-3
 MAX_DEPTH = 80
@@ -169,3 +181,156 @@ def eval_depth(disp, gt_depth, stereo_scale=False, min_depth=0.1, max_depth=100,
     scale = mg[1] / mp[1] if (s[7] > 0 and mp[1] != 0) else float("nan")
     return dict(abs_rel=abs_rel, sq_rel=sq_rel, rmse=rmse, rmse_log=rmse_log, a1=a1, a2=a2, a3=a3, scale=scale,
                 n_valid=int(s[7]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# KITTI odometry evaluation (mono/tools/kitti_evaluation_toolkit.py, scripts/plot_kitti.py) on csrc/odometry.hip
+ODOM_LENGTHS = (100, 200, 300, 400, 500, 600, 700, 800)
+ALIGN_MODES = ("umeyama_scale", "scale", "scale_7dof", "7dof", "6dof", "none")
+_I12 = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def _traj(p, name="poses"):
+    if not (isinstance(p, torch.Tensor) and p.is_cuda):
+        raise RuntimeError(f"odometry evaluation runs HIP kernels: {name} must be a CUDA tensor")
+    if p.dim() != 2 or p.shape[1] != 12 or p.shape[0] < 1 or p.dtype != torch.float64:
+        raise ValueError(f"{name} must be an (n,12) float64 trajectory with n >= 1, got {tuple(p.shape)} {p.dtype}")
+    return p.contiguous()
+
+
+def _host_doubles(values):
+    a = (ctypes.c_double * len(values))(*[float(v) for v in values])
+    return a, ctypes.addressof(a)
+
+
+def _ws(name, device, *args):
+    nbytes = lib().fn[name](*args)
+    if nbytes <= 0:
+        raise RuntimeError(f"{name}{args}: {lib().last_error()}")
+    return torch.empty(nbytes, device=device, dtype=torch.uint8)
+
+
+def traj_moments(x, y) -> np.ndarray:
+    """The 19 sums of jp_traj_moments over the positions of two equally long trajectories, as float64 numpy:
+    mean_x (3), mean_y (3), sigma_x^2, cov (9, row-major), sum x.y, sum x.x, sum |x - y|^2."""
+    x, y = _traj(x, "x"), _traj(y, "y")
+    if x.shape[0] != y.shape[0]:
+        raise ValueError(f"trajectories of different lengths: {x.shape[0]} vs {y.shape[0]}")
+    n = x.shape[0]
+    out = torch.empty(19, device=x.device, dtype=torch.float64)
+    call("jp_traj_moments", x, y, n, out, _ws("jp_traj_moments_ws_bytes", x.device, n))
+    return out.cpu().numpy()
+
+
+def transform_poses(poses, A=None, scale=1.0):
+    """out_k = A . [R_k | scale t_k] for an (n,12) device trajectory; A: 12 or (3,4) host numbers (None: the identity)."""
+    poses = _traj(poses)
+    keep, addr = _host_doubles(_I12 if A is None else np.asarray(A, dtype=np.float64).reshape(-1)[:12])
+    out = torch.empty_like(poses)
+    call("jp_poses_transform_f64", poses, poses.shape[0], addr, float(scale), out)
+    return out
+
+
+def _umeyama_from_moments(m, with_scale):
+    """Umeyama 1991, eq. 34-43, from the moments: rotation U S V^T of the covariance's SVD with S = diag(1, 1, det U det V^T)
+    (eq. 39, 40, 43), c = tr(D S) / sigma_x^2 (eq. 42), t = mean_y - c R mean_x (eq. 41)."""
+    mean_x, mean_y, var_x, cov = m[0:3], m[3:6], m[6], m[7:16].reshape(3, 3)
+    U, D, Vt = np.linalg.svd(cov)
+    S = np.ones(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0.0:
+        S[2] = -1.0
+    R = (U * S) @ Vt
+    c = float((D * S).sum() / var_x) if with_scale else 1.0
+    t = mean_y - c * (R @ mean_x)
+    return R, t, c
+
+
+def umeyama_alignment(x_poses, y_poses, with_scale=False):
+    """(R, t, c) minimising sum |y - (c R x + t)|^2 over the positions of two (n,12) device trajectories, float64 numpy."""
+    return _umeyama_from_moments(traj_moments(x_poses, y_poses), with_scale)
+
+
+def _rebase(poses):
+    """inv(pose_0) @ pose_k (plot_kitti.py:192-195, 218-221); the 4x4 inverse of the first pose is taken on the host."""
+    g = np.identity(4)
+    g[:3] = poses[0].cpu().numpy().reshape(3, 4)
+    return transform_poses(poses, np.linalg.inv(g)[:3], 1.0)
+
+
+def align_poses(pred, gt, mode="umeyama_scale"):
+    """Align the (n,12) device trajectory `pred` to `gt` -> (aligned (n,12) device float64, parameters).  parameters: `R` (3,3),
+    `t` (3), `scale` as used, and `reference`: the trajectory the aligned one is to be compared with (gt itself, or gt re-based to
+    its first pose for the plot_kitti modes, which re-base both)."""
+    pred, gt = _traj(pred, "pred"), _traj(gt, "gt")
+    if pred.shape[0] != gt.shape[0]:
+        raise ValueError(f"pred and gt must have the same number of poses, got {pred.shape[0]} and {gt.shape[0]}")
+    if mode not in ALIGN_MODES:
+        raise ValueError(f"align mode {mode!r}: expected one of {ALIGN_MODES}")
+    R, t, c = np.identity(3), np.zeros(3), 1.0
+    if mode == "none":
+        return pred, dict(R=R, t=t, scale=c, reference=gt)
+    if mode == "umeyama_scale":
+        _, _, c = umeyama_alignment(pred, gt, True)
+        return transform_poses(pred, None, c), dict(R=R, t=t, scale=c, reference=gt)
+    pred0, gt0 = _rebase(pred), _rebase(gt)
+    m = traj_moments(pred0, gt0)
+    if mode == "scale":
+        c = float(m[16] / m[17])                       # scale_lse_solver: sum(X * Y) / sum(X ** 2)
+        return transform_poses(pred0, None, c), dict(R=R, t=t, scale=c, reference=gt0)
+    Ru, tu, c = _umeyama_from_moments(m, mode != "6dof")
+    if mode == "scale_7dof":                           # only the translations are scaled
+        return transform_poses(pred0, None, c), dict(R=R, t=t, scale=c, reference=gt0)
+    return transform_poses(pred0, np.concatenate([Ru, tu[:, None]], 1), c), dict(R=Ru, t=tu, scale=c, reference=gt0)
+
+
+def odometry_segments(pred, gt, lengths=ODOM_LENGTHS, step=10):
+    """calcSequenceErrors on two (n,12) device trajectories -> (table (m,5) float64 numpy in the reference's order, rows
+    [first_frame, r_err/len, t_err/len, len, speed]; last_frame (S, nlen) int32 numpy, -1 = sequence too short; dist (n) numpy)."""
+    pred, gt = _traj(pred, "pred"), _traj(gt, "gt")
+    if pred.shape[0] != gt.shape[0]:
+        raise ValueError(f"pred and gt must have the same number of poses, got {pred.shape[0]} and {gt.shape[0]}")
+    n, nlen, step = gt.shape[0], len(lengths), int(step)
+    if not 1 <= nlen <= 16:
+        raise ValueError("between 1 and 16 segment lengths per call")
+    if step <= 0:
+        raise ValueError("step must be positive")
+    S = (n + step - 1) // step
+    keep, addr = _host_doubles(lengths)
+    dist = torch.empty(n, device=gt.device, dtype=torch.float64)
+    last = torch.empty(S * nlen, device=gt.device, dtype=torch.int32)
+    table = torch.empty((S * nlen, 5), device=gt.device, dtype=torch.float64)
+    call("jp_odom_segment_errors", gt, pred, n, step, addr, nlen, dist, last, table,
+         _ws("jp_odom_segments_ws_bytes", gt.device, n, step, nlen))
+    last = last.cpu().numpy()
+    return table.cpu().numpy()[last >= 0], last.reshape(S, nlen), dist.cpu().numpy()
+
+
+def _mean_tr(rows):
+    return [float(np.mean(rows[:, 2])), float(np.mean(rows[:, 1]))] if len(rows) else []
+
+
+def eval_odometry(pred, gt, align="umeyama_scale", lengths=ODOM_LENGTHS, step=10):
+    """kittiOdomEval.eval for one sequence (kitti_evaluation_toolkit.py:554-630) on (n,12) float64 device trajectories -> dict:
+    t_err, r_err     computeOverallErr: plain means of the table's t_err/len and r_err/len (printed as t_err * 100 % and
+                     r_err * 180 / pi deg/m); NaN with a RuntimeWarning when no segment qualifies (the reference divides by zero)
+    segments         the table, (n_segments, 5) numpy; n_segments
+    per_length       computeSegmentErr: {len: [t, r] or []};  per_speed: computeSpeedErr: {2, 4, .., 24 m/s: [t, r] or []}
+    distance, max_speed (m/s), scale (of the alignment), ate = sqrt(sum |x - y|^2 / n) of the aligned trajectory."""
+    pred, gt = _traj(pred, "pred"), _traj(gt, "gt")
+    if pred.shape[0] != gt.shape[0]:
+        raise ValueError(f"pred and gt must have the same number of poses, got {pred.shape[0]} and {gt.shape[0]}")
+    aligned, prm = align_poses(pred, gt, align)
+    seg, last, dist = odometry_segments(aligned, gt, lengths, step)
+    n = gt.shape[0]
+    if len(seg):
+        t_err, r_err = float(np.mean(seg[:, 2])), float(np.mean(seg[:, 1]))
+    else:
+        import warnings
+        warnings.warn("odometry errors over an empty set of segments (trajectory shorter than every length): returning NaN",
+                      RuntimeWarning)
+        t_err = r_err = float("nan")
+    per_length = {ln: _mean_tr(seg[seg[:, 3] == float(ln)]) for ln in lengths}
+    per_speed = {s: _mean_tr(seg[np.abs(seg[:, 4] - s) < 2.0]) for s in range(2, 25, 2)}
+    ate = math.sqrt(traj_moments(aligned, prm["reference"])[18] / n)
+    return dict(t_err=t_err, r_err=r_err, segments=seg, n_segments=int(len(seg)), per_length=per_length, per_speed=per_speed,
+                distance=float(dist[-1]), max_speed=float(seg[:, 4].max()) if len(seg) else 0.0, scale=float(prm["scale"]), ate=ate)

@@ -119,6 +119,25 @@ GROUPS = [
      "road and the car head (B, 2, HW; strictly-greater, ties -> 0; car_logits nullable) -> cls (B, HW) bytes 0 / 1 road / 2 car "
      "and (nullable) rgb (B, HW, 3) with the palette (0,0,0) / (255,255,255) / (0,0,255) (:157-161,195-218).",
      ["jp_disp_resize_depth", "jp_quantiles_ws_bytes", "jp_quantiles", "jp_colorize_u8", "jp_layout_classes_u8"]),
+    ("KITTI odometry evaluation (csrc/odometry.hip; core/evaluation.py::eval_odometry, apis/inference.py) — the pose chaining of "
+     "scripts/draw_odometry.py:62-76 and the numpy toolkit behind the paper's t_err / r_err (mono/tools/kitti_evaluation_toolkit.py:"
+     "109-201, mono/tools/geometry.py:20-67, scripts/plot_kitti.py:15-97,223-243).  All arithmetic is double, no atomics: every sum "
+     "and product is folded in an order that depends on n alone (two runs are bit-identical); scans are three launches (block-local, "
+     "one workgroup over the block aggregates, apply), no workgroup waits on another.  A pose is the 12 doubles of rows 0..2 of a 4x4, "
+     "the KITTI text layout.  jp_pose_chain_f64: T (n,4,4) float frame-to-frame transforms as jp_pose_fwd writes them (row 3 is not "
+     "read: 0 0 0 1) -> poses (n+1,12), G_0 = I, G_k = G_{k-1} M_k with M_k = T_k^-1 (invert != 0; the GENERAL affine inverse, "
+     "adjugate / determinant, not the transpose) or T_k; ws: jp_pose_chain_ws_bytes(n) bytes.  jp_odom_segment_errors: gt / pred (n,12); "
+     "lengths: HOST array of nlen <= 16 positive lengths in metres; dist (n) = trajectoryDistances of gt; with S = ceil(n / step) start "
+     "frames s step: last_frame (S nlen) = first i >= first with dist[i] > dist[first] + len (bisection; -1: the sequence is too short), "
+     "table (S nlen, 5) rows [first_frame, r_err / len, t_err / len, len, speed] of calcSequenceErrors, untouched where last_frame is -1; "
+     "r_err = acos(clamp((trace - 1) / 2, -1, 1)), speed = len / (0.1 (last - first + 1)); ws: jp_odom_segments_ws_bytes(n, step, nlen) "
+     "bytes.  jp_traj_moments: positions (columns 3, 7, 11) of x / y (n,12) -> out (19): mean_x, mean_y, sigma_x^2 = 1/n sum |x - "
+     "mean_x|^2, cov = 1/n sum (y - mean_y)(x - mean_x)^T (row-major), sum x.y, sum x.x, sum |x - y|^2 -- two passes, means first "
+     "(Umeyama eq. 34-38; plot_kitti's scale; the ATE); ws: jp_traj_moments_ws_bytes(n) bytes.  jp_poses_transform_f64: "
+     "out_k = A [R_k | scale t_k], A: HOST array of 12 doubles; A = I is traj.scale(scale) exactly; out may be poses.  Scratch need "
+     "not be initialised.",
+     ["jp_pose_chain_ws_bytes", "jp_pose_chain_f64", "jp_odom_segments_ws_bytes", "jp_odom_segment_errors", "jp_traj_moments_ws_bytes",
+      "jp_traj_moments", "jp_poses_transform_f64"]),
     ("Device-side input pipeline — MonoDataset.preprocess mono/datasets/mono_dataset.py:126-171 (PIL ANTIALIAS resize, bit-exact "
      "Pillow fixed-point resampler; ToTensor; ColorJitter in torchvision tensor arithmetic) and process_topview :417-431, applied "
      "to raw uint8 frames after one pinned async upload.",

@@ -140,8 +140,22 @@ GROUPS = [
       "jp_traj_moments", "jp_poses_transform_f64"]),
     ("Device-side input pipeline — MonoDataset.preprocess mono/datasets/mono_dataset.py:126-171 (PIL ANTIALIAS resize, bit-exact "
      "Pillow fixed-point resampler; ToTensor; ColorJitter in torchvision tensor arithmetic) and process_topview :417-431, applied "
-     "to raw uint8 frames after one pinned async upload.",
-     ["jp_resample_h_u8", "jp_resample_v_u8", "jp_u8_to_tensor", "jp_color_jitter_op", "jp_topview_u8"]),
+     "to raw uint8 frames after one pinned async upload.  *_flip: MonoDataset.__getitem__'s do_flip (mono_dataset.py:203; every getter's "
+     "transpose(pil.FLIP_LEFT_RIGHT) of the raw image / BEV label BEFORE any resize) per item of a batch: flip = N bytes in device memory, "
+     "non-zero = mirror that item left-right before the operation, NULL = no item; with NULL or all-zero flags the output is bit-identical "
+     "to the plain entry point's.  jp_resample_h_u8_flip: jp_resample_h_u8 over N items of H rows, a flagged item's tap k of output "
+     "column ox reads source column W-1-(xmin+k) (= resizing the mirrored image, bit for bit).  jp_u8_to_tensor_flip: no horizontal "
+     "resize -- writes the float CHW / 255 tensor (dst_f) and / or the mirrored uint8 HWC image (dst_u8); either may be NULL, not both; "
+     "dst_u8 != src.  jp_topview_u8_flip: the NEAREST pick of jp_topview_u8 on the mirrored label (column w-1-sx).  "
+     "jp_color_jitter_batched: ColorJitter on N images (N,3,HW) in place, two launches whatever N is; params (N, 9) int32 in device "
+     "memory, one record per image: n_ops (0..4; 0 = the image is not written), order[4] (op ids 0 brightness / 1 contrast / "
+     "2 saturation / 3 hue in the order they are applied, contrast at most once), factor[4] (bit patterns of the floats, factor[j] "
+     "belongs to order[j]).  Contrast blends with the gray mean of the image as it stands after the ops before it: the first launch "
+     "recomputes those per pixel and leaves per-workgroup partial sums in ws (jp_color_jitter_batched_ws_doubles(N, HW) doubles of "
+     "caller scratch, need not be initialised), the second folds them in a fixed order -- no atomics, two runs give the same bits "
+     "(jp_color_jitter_op folds its gray sum with atomic adds).",
+     ["jp_resample_h_u8", "jp_resample_v_u8", "jp_u8_to_tensor", "jp_color_jitter_op", "jp_topview_u8", "jp_resample_h_u8_flip",
+      "jp_u8_to_tensor_flip", "jp_topview_u8_flip", "jp_color_jitter_batched_ws_doubles", "jp_color_jitter_batched"]),
     ("Library plumbing.  jp_profile_*: opt-in per-kernel HIP-event timing of the implicit-GEMM launches on the streams they "
      "are launched on (bench.py's roofline leg; never active in the train step).",
      ["jp_abi_version", "jp_last_error_string", "jp_set_last_error", "jp_profile_begin", "jp_profile_count", "jp_profile_end",

@@ -23,7 +23,7 @@ _CT = {
 
 
 _PTR_DTYPE = {"float*": torch.float32, "double*": torch.float64, "int*": torch.int32, "int64_t*": torch.int64,
-              "long*": torch.int64, "uint8_t*": torch.uint8}
+              "long*": torch.int64, "uint8_t*": torch.uint8, "long long*": torch.int64, "unsigned char*": torch.uint8}
 
 
 class JPerceiverHipError(RuntimeError):

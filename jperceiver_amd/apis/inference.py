@@ -4,6 +4,10 @@
         scripts/eval_depth_eigen.py:24-113: eval-mode forward -> ("disp", 0, 0) -> disp_to_depth(0.1, 100) -> resize to the
         ground truth -> 1/disp, range mask (0.1 .. 80 m) + Garg crop, per-image median scaling (or the fixed stereo
         factor 1), clamp, the seven depth metrics; returns (mean errors, median ratio, std of ratios / median).
+    evaluate_depth_lidar(model, batches, scans, calib, batch=8, stereo_scale=False)
+        evaluate_depth with the ground truth built on the device from Velodyne scans (core.evaluation.lidar_depth_maps, the
+        reference's generate_depth_map) and the images scored `batch` at a time (core.evaluation.eval_depth_batch); images are
+        grouped by ground-truth size, which differs between KITTI drives.  Same triple.
     pose_between(pose_encoder, pose_decoder, img_a, img_b)
         the 4x4 transform `transformation_from_parameters(axisangle[:, 0], translation[:, 0])` of
         scripts/draw_odometry.py:69-71 for one pair (both images concatenated on channels, frame 0 first).
@@ -57,6 +61,76 @@ def evaluate_depth(model, batches, gt_depths, stereo_scale=False, min_depth=0.1,
     med = float(np.median(ratios))
     return dict(zip(("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3"), np.asarray(errors).mean(0).tolist())), med, \
         float(np.std(ratios / med))
+
+
+_ERR_KEYS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
+
+
+def _calib_entry(c, cam):
+    if isinstance(c, (str, bytes)) or hasattr(c, "__fspath__"):
+        from ..datasets.kitti_calib import velo_to_image
+        return velo_to_image(c, cam)
+    P, hw = c
+    return np.asarray(P, dtype=np.float64).reshape(3, 4), (int(hw[0]), int(hw[1]))
+
+
+@torch.no_grad()
+def evaluate_depth_lidar(model, batches, scans, calib, batch=8, stereo_scale=False, min_depth=0.1, max_depth=80.0, cam=2,
+                         vel_depth=False):
+    """batches: as for evaluate_depth; scans: one (N, 4) float32 Velodyne scan (array, tensor, or the path of a .bin file) per IMAGE,
+    in the order the images come; calib: one entry for all images or one per image, each a calibration directory (read with
+    datasets.kitti_calib.velo_to_image for camera `cam`) or a (P (3,4), (H, W)) pair.  Up to `batch` images of one ground-truth size
+    are turned into depth maps by one jp_lidar_depth_map call and scored by one jp_depth_eval_batch call."""
+    _eval(model)
+    if int(batch) < 1:
+        raise ValueError("batch must be at least 1")
+    scans = list(scans)
+    one_calib = isinstance(calib, (str, bytes)) or hasattr(calib, "__fspath__") or (
+        isinstance(calib, tuple) and len(calib) == 2 and np.ndim(calib[0]) == 2)
+    cache = {}
+
+    def calib_of(i):
+        c = calib if one_calib else calib[i]
+        key = c if isinstance(c, (str, bytes)) else id(c)
+        if key not in cache:
+            cache[key] = _calib_entry(c, cam)
+        return cache[key]
+
+    results, pending = {}, {}
+
+    def flush(key):
+        items = pending.pop(key)
+        gt = ev.lidar_depth_maps([it[2] for it in items], np.stack([it[3] for it in items]), key[0], vel_depth=vel_depth,
+                                 dtype=torch.float32, device=items[0][1].device)
+        res = ev.eval_depth_batch(torch.cat([it[1] for it in items], 0), gt, stereo_scale=stereo_scale, min_depth=0.1, max_depth=100,
+                                  mask_min=min_depth, mask_max=max_depth, stereo_factor=1.0)
+        for it, r in zip(items, res):
+            results[it[0]] = r
+
+    i = 0
+    for inputs in batches:
+        disp = model(inputs)[("disp", 0, 0)]
+        for b in range(disp.shape[0]):
+            if i >= len(scans):
+                raise ValueError(f"{len(scans)} scans for more images")
+            pts = scans[i]
+            if isinstance(pts, (str, bytes)) or hasattr(pts, "__fspath__"):
+                from ..datasets.kitti_calib import load_velodyne_points
+                pts = load_velodyne_points(pts)
+            P, hw = calib_of(i)
+            key = (hw, tuple(disp.shape[2:]))
+            pending.setdefault(key, []).append((i, disp[b:b + 1], pts, P))
+            if len(pending[key]) == int(batch):
+                flush(key)
+            i += 1
+    for key in list(pending):
+        flush(key)
+    if not results:
+        raise ValueError("no image to evaluate")
+    errors = [[results[j][k] for k in _ERR_KEYS] for j in range(i)]
+    ratios = np.asarray([results[j]["scale"] for j in range(i)])
+    med = float(np.median(ratios))
+    return dict(zip(_ERR_KEYS, np.asarray(errors).mean(0).tolist())), med, float(np.std(ratios / med))
 
 
 @torch.no_grad()

@@ -9,7 +9,15 @@ mono/core/evaluation/eval_hooks.py:147-199), computed by GPU reductions of libjp
     eval_depth(disp, gt_depth)          the hook's per-sample depth block (eval_hooks.py:147-179): scaled disparity ->
                                         bilinear resize to the ground-truth size -> depth, range mask + Garg crop, median
                                         scaling (or the fixed x36 stereo scale), clamp, compute_errors -> dict incl. 'scale'
+    eval_depth_batch(disp, gt_depths)   eval_depth for B samples of one ground-truth size in four launches and one device-to-host copy
+                                        (jp_depth_eval_batch): exact medians, sums folded in a fixed order -> list of the same dicts
     disp_to_depth, AverageMeter         as in pixel_error.py
+
+and the depth ground truth of the Eigen split from Velodyne scans (mono/datasets/kitti_utils.py:50-102), csrc/lidar.hip:
+
+    lidar_depth_maps(points, P, hw)     B scans -> (B, H, W) device maps in one call: the closest return per pixel in float64, incl. the
+                                        reference's shared key of pixel (r, W-1) and pixel (r+1, 0) (see csrc/lidar.hip)
+    generate_depth_map(calib_dir, velo_filename, cam, vel_depth)   the reference's signature on KITTI files -> one (H, W) device map
 
 and the KITTI odometry evaluation of mono/tools/kitti_evaluation_toolkit.py (`kittiOdomEval.eval`, the paper's t_err / r_err) with
 the alignment modes of scripts/plot_kitti.py, on (n,12) float64 device trajectories (csrc/odometry.hip):
@@ -181,6 +189,85 @@ def eval_depth(disp, gt_depth, stereo_scale=False, min_depth=0.1, max_depth=100,
     scale = mg[1] / mp[1] if (s[7] > 0 and mp[1] != 0) else float("nan")
     return dict(abs_rel=abs_rel, sq_rel=sq_rel, rmse=rmse, rmse_log=rmse_log, a1=a1, a2=a2, a3=a3, scale=scale,
                 n_valid=int(s[7]))
+
+
+def _garg_crop(H, W):
+    crop = np.array([0.40810811 * H, 0.99189189 * H, 0.03594771 * W, 0.96405229 * W]).astype(np.int32)
+    return int(crop[0]), int(crop[1]), int(crop[2]), int(crop[3])
+
+
+def eval_depth_batch(disp, gt_depths, stereo_scale=False, min_depth=0.1, max_depth=100, mask_min=MIN_DEPTH, mask_max=MAX_DEPTH,
+                     stereo_factor=36.0):
+    """eval_depth for a batch: disp (B,1,h,w), gt_depths (B,H,W) -> list of B dicts with eval_depth's keys.  n_valid, the medians
+    (hence `scale`) and the a1 / a2 / a3 counts are those of B eval_depth calls bit for bit; the four float64 error sums are
+    folded in a fixed order (bit-identical from run to run) and differ from eval_depth's atomically merged ones by reordering only."""
+    disp, gt = _dev(disp), _dev(gt_depths)
+    if disp.dim() != 4 or disp.shape[1] != 1 or gt.dim() != 3 or gt.shape[0] != disp.shape[0] or disp.shape[0] < 1:
+        raise ValueError(f"expected disp (B,1,h,w) and gt_depths (B,H,W), got {tuple(disp.shape)} and {tuple(gt.shape)}")
+    B, _, h, w = disp.shape
+    H, W = gt.shape[1:]
+    y0, y1, x0, x1 = _garg_crop(H, W)
+    out = torch.empty(B * 10, device=disp.device, dtype=torch.float64)            # sums (B,8) | med (B,4) floats: one copy back
+    sums, med = out[:B * 8], out[B * 8:].view(torch.float32)
+    call("jp_depth_eval_batch", disp, gt, B, h, w, H, W, y0, y1, x0, x1, float(mask_min), float(mask_max), float(min_depth),
+         float(max_depth), float(stereo_factor) if stereo_scale else 0.0, sums, med,
+         _ws("jp_depth_eval_batch_ws_bytes", disp.device, B, H, W))
+    host = out.cpu()
+    s_all, m_all = host[:B * 8].reshape(B, 8).tolist(), host[B * 8:].view(torch.float32).reshape(B, 4).tolist()
+    res = []
+    for s, m in zip(s_all, m_all):
+        abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 = _errors_from_sums(s)
+        scale = m[1] / m[3] if (s[7] > 0 and m[3] != 0) else float("nan")
+        res.append(dict(abs_rel=abs_rel, sq_rel=sq_rel, rmse=rmse, rmse_log=rmse_log, a1=a1, a2=a2, a3=a3, scale=scale,
+                        n_valid=int(s[7])))
+    return res
+
+
+def lidar_depth_maps(points, P, hw, flip=None, vel_depth=False, dtype=torch.float64, device=None):
+    """Depth ground truth of B Velodyne scans in one call (jp_lidar_depth_map; kitti_utils.py:50-102 per scan).
+    points: list of B (N_b, 4) float32 arrays / tensors (x, y, z, reflectance; N_b may be 0 and may differ); P: (3,4) or (B,3,4)
+    float64 velodyne -> image matrices (datasets.kitti_calib.velo_to_image); hw: (H, W) of the maps; flip: B booleans (mirror the
+    finished map left-right) or None; dtype float64 or float32 (the rounded float64 map) -> (B, H, W) device tensor."""
+    if dtype not in (torch.float64, torch.float32):
+        raise ValueError("dtype must be torch.float64 or torch.float32")
+    B = len(points)
+    if B < 1:
+        raise ValueError("at least one scan")
+    H, W = int(hw[0]), int(hw[1])
+    scans = [p if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p, dtype=np.float32)) for p in points]
+    for p in scans:
+        if p.dim() != 2 or p.shape[1] != 4 or p.dtype != torch.float32:
+            raise ValueError(f"every scan must be an (N, 4) float32 array, got {tuple(p.shape)} {p.dtype}")
+    if device is None:
+        device = next((p.device for p in scans if p.is_cuda), torch.device("cuda"))
+    counts = [int(p.shape[0]) for p in scans]
+    offsets = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int64).to(device)
+    pts = torch.cat([p.to(device) for p in scans], 0).contiguous()
+    if pts.shape[0] == 0:
+        pts = torch.zeros((1, 4), device=device)                                  # a valid pointer; no row is read
+    Pm = torch.as_tensor(np.asarray(P.cpu() if isinstance(P, torch.Tensor) else P, dtype=np.float64))
+    if tuple(Pm.shape) == (3, 4):
+        Pm = Pm.expand(B, 3, 4)
+    if tuple(Pm.shape) != (B, 3, 4):
+        raise ValueError(f"P must be (3,4) or ({B},3,4), got {tuple(Pm.shape)}")
+    Pm = Pm.contiguous().to(device)
+    fl = None
+    if flip is not None:
+        fl = torch.as_tensor(np.asarray(flip.cpu() if isinstance(flip, torch.Tensor) else flip).astype(bool).astype(np.uint8))
+        if tuple(fl.shape) != (B,):
+            raise ValueError(f"flip must hold {B} flags")
+        fl = fl.to(device)
+    out = torch.empty((B, H, W), device=device, dtype=dtype)
+    call("jp_lidar_depth_map", pts, offsets, Pm, fl, B, H, W, 1 if vel_depth else 0, out if dtype == torch.float64 else None,
+         out if dtype == torch.float32 else None, _ws("jp_lidar_depth_ws_bytes", device, B, H, W))
+    return out
+
+
+def generate_depth_map(calib_dir, velo_filename, cam=2, vel_depth=False):
+    """kitti_utils.py:50-102 on KITTI files -> the (H, W) float64 map on the device."""
+    from ..datasets.kitti_calib import load_velodyne_points, velo_to_image
+    P, hw = velo_to_image(calib_dir, cam)
+    return lidar_depth_maps([load_velodyne_points(velo_filename)], P, hw, vel_depth=vel_depth)[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

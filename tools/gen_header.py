@@ -105,6 +105,26 @@ GROUPS = [
      "of argmax(logits) vs label); depth compute_errors + median scaling + Garg crop mono/core/evaluation/pixel_error.py:27-40, "
      "mono/core/evaluation/eval_hooks.py:147-179.",
      ["jp_confusion2", "jp_depth_eval_prepare", "jp_masked_median", "jp_depth_errors"]),
+    ("Batched depth scoring and LiDAR ground truth (csrc/evalmetrics.hip, csrc/lidar.hip; core/evaluation.py::eval_depth_batch, "
+     "lidar_depth_maps).  jp_depth_eval_batch: the chain of eval_depth (jp_affine -> jp_bilinear_fwd -> jp_depth_eval_prepare -> "
+     "jp_masked_median x 2 -> jp_depth_errors) for B images in four launches, the same float32 operations per pixel: disp (B,1,h,w), "
+     "gt (B,H,W); min_depth / max_depth are doubles because the two constants of disp_to_depth are formed in double and rounded to "
+     "float once, as the Python chain does; crop rows y0..y1-1, columns x0..x1-1; fixed_scale > 0 replaces the median ratio.  sums "
+     "(B,8) as jp_depth_errors defines them, med (B,4) = {n, median gt, n, median pred}: the medians are exact (radix selection, bit-"
+     "equal to jp_masked_median), the sums are folded from per-workgroup partials in a fixed order, no floating-point atomics -- two "
+     "runs give the same bits.  ws: jp_depth_eval_batch_ws_bytes(B, H, W) bytes, need not be initialised.  "
+     "jp_lidar_depth_map: mono/datasets/kitti_utils.py::generate_depth_map for B scans in float64.  pts (sum N_b, 4) x, y, z, "
+     "reflectance (not read: w = 1); offsets (B+1) in device memory, item b owns rows offsets[b] .. offsets[b+1]-1; P (B,3,4) "
+     "velodyne -> image (P_rect R_rect velo2cam); flip (B) bytes or NULL: mirror the finished map left-right.  Points with x < 0 are "
+     "dropped; u = rint(q0/q2) - 1, v = rint(q1/q2) - 1 (ties to even) must lie inside the image; d = q2 (vel_depth: the point's x); "
+     "a pixel holds the minimum d of its points, 0 without one; negative values become 0 after the minimum.  THE QUIRK of the "
+     "reference, kept because every gt_depths.npz in circulation carries it: its duplicate search gives pixel (r, W-1) and pixel "
+     "(r+1, 0) one key, so when both hold points the one that owns the earliest point of the pair (file order) gets the minimum over "
+     "the points of both and the other keeps the d of its own last point.  Only columns 0 and W-1 are affected (outside the Garg "
+     "crop); W >= 2.  out64 / out32 (B,H,W): either may be NULL, not both; out32 is the rounded out64.  64-bit integer atomic minima "
+     "on the ordered image of the double: the result does not depend on scheduling.  ws: jp_lidar_depth_ws_bytes(B, H, W) bytes; ws "
+     "and the outputs need not be initialised.",
+     ["jp_depth_eval_batch_ws_bytes", "jp_depth_eval_batch", "jp_lidar_depth_ws_bytes", "jp_lidar_depth_map"]),
     ("Video perception post-processing (csrc/perception.hip; apis/perception.py) — what scripts/eval_kitti_video.py does in host numpy "
      "on copied-back tensors.  jp_disp_resize_depth: disp_to_depth's scaled disparity 1/max_depth + (1/min_depth - 1/max_depth) disp, "
      "half-pixel bilinear resize to OH x OW (cv2.resize INTER_LINEAR; the sampling rule of jp_bilinear_fwd) and 1/x in one pass "

@@ -23,6 +23,12 @@
         odometry() with the pairs run `batch` at a time and the chain on the device: (n,3,H,W) -> (n, 12) device float64.
     evaluate_odometry(pose_encoder, pose_decoder, frames, gt_poses, batch=8, **eval_kw)
         odometry_device + core.evaluation.eval_odometry (mono/tools/kitti_evaluation_toolkit.py: the paper's t_err / r_err).
+    freeze(model_or_module) / unfreeze(module)
+        frozen inference: every eval-mode `conv -> BatchNorm2d` pair below the module (the three ResNet-18 encoders, the BEV
+        decoders) is folded into one convolution (jp_bn_fold_conv, once) and the residual blocks end in one relu(a + b) pass
+        (jp_add_relu) -- no BatchNorm pass over any activation map.  Opt-in; every helper here and apis.Perceiver work on a
+        frozen model as on any other.  Weights that change afterwards (load_state_dict, in-place edits, an optimizer step, a
+        train-mode forward) are folded again by the next forward; train mode ignores the frozen state.
     read_kitti_poses(path) / write_kitti_poses(path, poses)
         the KITTI pose text file: 12 numbers per line, or 13 with a leading frame index (loadPoses); written with '%1.8e'
         like the script (draw_odometry.py:78).
@@ -35,12 +41,30 @@ import torch
 
 from .._lib import call, lib
 from ..core import evaluation as ev
+from ..model import modules as _modules
 
 
 def _eval(*mods):
     for m in mods:
         if m.training:
             raise RuntimeError("inference helpers expect eval-mode networks (call .eval(): BatchNorm must use running stats)")
+
+
+def freeze(module):
+    """Fold every eligible conv/BatchNorm2d pair of an eval-mode model (or sub-network) and attach the folded state; returns the
+    same module.  The forward passes then take the frozen route while the module is in eval mode.
+
+    Each forward re-folds the pairs whose source tensors moved, as far as the host can see it: load_state_dict, in-place
+    tensor operations, optimizer steps and train-mode forwards are seen.  A write through `.data` (or by foreign code through a
+    raw pointer) is NOT, exactly as for the packed-weight cache: call `jperceiver_amd.ops.weights_changed()` after one."""
+    if module.training:
+        raise RuntimeError("freeze expects an eval-mode model (call .eval(): BatchNorm must use running stats)")
+    return _modules.freeze_module(module)
+
+
+def unfreeze(module):
+    """Remove the frozen state: the forward passes are the eval-mode BatchNorm route again.  Returns the module."""
+    return _modules.unfreeze_module(module)
 
 
 @torch.no_grad()

@@ -169,11 +169,15 @@ def layout_rgb(layout):
 
 class Perceiver:
     """Per-frame depth, BEV layout and ego-motion from an eval-mode `Baseline` that holds a checkpoint.
-    out_size: (OH, OW) of the depth maps (default: the network's resolution); min_depth / max_depth default to model.opt's."""
+    out_size: (OH, OW) of the depth maps (default: the network's resolution); min_depth / max_depth default to model.opt's.
+    frozen=True: `apis.freeze(model)` first -- BatchNorm folded into the convolutions (the model stays frozen afterwards)."""
 
-    def __init__(self, model, out_size=None, min_depth=None, max_depth=None):
+    def __init__(self, model, out_size=None, min_depth=None, max_depth=None, frozen=False):
         if model.training:
             raise RuntimeError("Perceiver expects an eval-mode model (call .eval(): BatchNorm must use running stats)")
+        if frozen:
+            from .inference import freeze
+            freeze(model)
         self.model = model
         self.out_size = None if out_size is None else (int(out_size[0]), int(out_size[1]))
         self.min_depth = float(model.opt.min_depth if min_depth is None else min_depth)

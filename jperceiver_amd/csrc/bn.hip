@@ -673,7 +673,9 @@ extern "C" int jp_bn_eval_fwd(const float* x, const float* gamma, const float* b
     JP_CHECK_ARG(x && gamma && beta && running_mean && running_var && y && N > 0 && C > 0 && HW > 0, "bn_eval_fwd: bad args");
     hipStream_t st = (hipStream_t)stream;
     const int gx = std::min(jp_cdiv(HW, 4 * TPB), 64);
+    jp_prof_before("jp_bn_eval_fwd", 0.0, st);       // (a no-op unless a profile is open: tools/frozen_bench.py; 0 FLOPs: no GEMM)
     hipLaunchKernelGGL(bn_eval_kernel, dim3(gx, N * C), dim3(TPB), 0, st, x, running_mean, running_var, gamma, beta,
                        residual, y, C, HW, eps, relu);
+    jp_prof_after(st);
     JP_LAUNCH_CHECK();
 }

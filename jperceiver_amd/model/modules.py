@@ -34,6 +34,7 @@ class BatchNorm2d(nn.BatchNorm2d):
     def __init__(self, c):
         super().__init__(c)
         self._pending = 0
+        self._updates = 0       # train-mode forwards so far: their kernels rewrite the running statistics (FrozenConvBN's staleness check)
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         if self._pending:
@@ -49,6 +50,7 @@ class BatchNorm2d(nn.BatchNorm2d):
 def bn_apply(bn: BatchNorm2d, x: Var, residual=None, relu=False, n_updates=1, groups=1) -> Var:
     if bn.training:
         bn._pending += n_updates * groups
+        bn._updates += 1
         return ops.batchnorm_train(x, P(bn.weight), P(bn.bias), bn.running_mean, bn.running_var, residual, relu,
                                    bn.momentum, bn.eps, n_updates, groups)
     return ops.batchnorm_eval(x, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, residual, relu, bn.eps)
@@ -61,6 +63,99 @@ def conv_apply(conv: nn.Conv2d, x, stride=None, pad=None, pad_mode=PAD_ZERO, act
     pad = conv.padding[0] if pad is None else pad
     return ops.conv2d(x, P(conv.weight), P(conv.bias) if conv.bias is not None else None, stride, pad, pad_mode, act,
                       srcs, bn_stats=bn_stats)
+
+
+# ------------------------------------------------------------------------------------------- frozen inference
+class FrozenConvBN:
+    """An eval-mode `conv -> BatchNorm2d` pair as ONE convolution: w' = w * s, b' = beta + (b - running_mean) * s with
+    s = gamma / sqrt(running_var + eps) per output channel (jp_bn_fold_conv, float64, each result rounded once), so the pair runs
+    as a single jp_conv2d_fwd* launch with its bias / activation epilogue and no pass over the activation map.
+
+    The folded tensors are held as parameters of their own (never trained, in no state dict) so that `ops.conv2d` packs them
+    once like any layer's weights.  They are a CACHE of six source tensors -- conv weight and bias, gamma, beta, running mean and
+    variance: `current()` compares, on the host, what it recorded of them at the last fold (identity, storage, version counter,
+    the count of ops.weights_changed() calls -- optimizer kernels, Baseline.load_state_dict, .to() -- and the BatchNorm's count
+    of train-mode forwards) and folds again when anything moved.  No device synchronisation either way.
+
+    What the check cannot see is a write that bypasses both autograd's version counter and ops.weights_changed(): an edit
+    through `.data` (`conv.weight.data.mul_(2)`), or a kernel of another library writing through a raw pointer.  That is the
+    weight-pack cache's contract too (ops.PackRegistry): call ops.weights_changed() after such a write, or unfreeze and freeze."""
+    __slots__ = ("conv", "bn", "w", "b", "_pw", "_pb", "_seen")
+
+    def __init__(self, conv: nn.Conv2d, bn: BatchNorm2d):
+        if not isinstance(conv, nn.Conv2d) or not isinstance(bn, BatchNorm2d):
+            raise ValueError("FrozenConvBN: expects a torch.nn.Conv2d and this module's BatchNorm2d (a plain torch.nn.BatchNorm2d "
+                             "does not count its train-mode forwards, so a stale fold could go unnoticed)")
+        if conv.out_channels != bn.num_features or conv.groups != 1 or conv.dilation[0] != 1 or conv.padding_mode != "zeros":
+            raise ValueError("FrozenConvBN: the BatchNorm does not sit behind this (plain, zero-padded) convolution")
+        if not (bn.affine and bn.track_running_stats):
+            raise ValueError("FrozenConvBN: the BatchNorm needs an affine map and running statistics")
+        self.conv, self.bn = conv, bn
+        self.w = self.b = self._pw = self._pb = self._seen = None
+
+    def _sources(self):
+        return (self.conv.weight, self.conv.bias, self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var)
+
+    def _state(self):
+        return tuple((None if t is None else (id(t), t.data_ptr(), t._version)) for t in self._sources()) + (
+            ops._WRITES[0], self.bn._updates, float(self.bn.eps))
+
+    def fold(self):
+        w = self.conv.weight.data
+        if not w.is_cuda:
+            raise RuntimeError("frozen inference folds on the GPU: its kernels are HIP (move the model there first)")
+        if self._pw is None or self._pw.device != w.device or self._pw.shape != w.shape:
+            self._pw = nn.Parameter(torch.empty_like(w, memory_format=torch.contiguous_format), requires_grad=False)
+            self._pb = nn.Parameter(torch.empty(w.shape[0], device=w.device, dtype=w.dtype), requires_grad=False)
+            self.w, self.b = Var(self._pw.data, False, None, self._pw), Var(self._pb.data, False, None, self._pb)
+        else:
+            ops.PackRegistry.of(w.device).invalidate(self._pw)       # folded in place: the packed copies are stale
+        cb = self.conv.bias.data if self.conv.bias is not None else None
+        Cout = w.shape[0]
+        ops.call("jp_bn_fold_conv", w.contiguous(), cb, self.bn.weight.data, self.bn.bias.data, self.bn.running_mean,
+                 self.bn.running_var, float(self.bn.eps), self._pw.data, self._pb.data, Cout, w.numel() // Cout)
+        self._seen = self._state()
+
+    def current(self):
+        if self._seen != self._state():
+            self.fold()
+        return self
+
+    def apply(self, x, act=ACT_NONE, srcs=None) -> Var:
+        return ops.conv2d(x, self.w, self.b, self.conv.stride[0], self.conv.padding[0], PAD_ZERO, act, srcs)
+
+
+def frozen_of(conv, bn):
+    """The pair's up-to-date frozen state when the frozen route applies (eval mode, `freeze_module` attached one), else None."""
+    fz = bn.__dict__.get("_frozen")
+    if fz is None or bn.training or fz.conv is not conv:
+        return None
+    return fz.current()
+
+
+def freeze_module(module: nn.Module) -> nn.Module:
+    """Attach a FrozenConvBN to every conv/BatchNorm2d pair below `module` (the classes that own such pairs list them in
+    `_conv_bn_pairs`) and fold it now if the weights are on the GPU (else at the first forward).  Eval mode only."""
+    pairs = [pr for m in module.modules() if hasattr(m, "_conv_bn_pairs") for pr in m._conv_bn_pairs()]
+    if module.training or any(bn.training for _, bn in pairs):
+        raise RuntimeError("freeze expects an eval-mode model (call .eval(): BatchNorm must use running stats)")
+    for conv, bn in pairs:
+        fz = bn.__dict__.get("_frozen")
+        if fz is None or fz.conv is not conv:
+            fz = bn.__dict__["_frozen"] = FrozenConvBN(conv, bn)
+        if conv.weight.is_cuda:
+            fz.current()
+    return module
+
+
+def unfreeze_module(module: nn.Module) -> nn.Module:
+    for m in module.modules():
+        m.__dict__.pop("_frozen", None)
+    return module
+
+
+def is_frozen(module: nn.Module) -> bool:
+    return any("_frozen" in m.__dict__ for m in module.modules())
 
 
 # ------------------------------------------------------------------------------------------- layers.py
@@ -219,7 +314,17 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
         self.stride = stride
 
+    def _conv_bn_pairs(self):
+        ds = [(self.downsample[0], self.downsample[1])] if self.downsample is not None else []
+        return [(self.conv1, self.bn1), (self.conv2, self.bn2)] + ds
+
     def _fwd(self, x, n_updates=1, groups=1):
+        fz = [frozen_of(c, b) for c, b in self._conv_bn_pairs()]
+        if all(f is not None for f in fz):
+            # frozen inference: conv1' + ReLU epilogue, conv2', (downsample'), then ONE pass relu(out + res) into conv2's own output
+            out = fz[1].apply(fz[0].apply(x, ACT_RELU))
+            res = fz[2].apply(x) if len(fz) > 2 else x
+            return ops.add_relu(out, res, inplace=True)
         tr = self.bn1.training and _BN_STATS_FUSE
         out = bn_apply(self.bn1, conv_apply(self.conv1, x, bn_stats=tr), relu=True, n_updates=n_updates, groups=groups)
         out = conv_apply(self.conv2, out, bn_stats=tr)
@@ -256,6 +361,9 @@ class ResNet(nn.Module):
             layers.append(BasicBlock(planes, planes))
         return nn.Sequential(*layers)
 
+    def _conv_bn_pairs(self):
+        return [(self.conv1, self.bn1)]
+
     def features(self, img: Var, n_updates=1, ready_tag=None, groups=1, need_f0=True):
         """(x-0.45)/0.225 -> stem -> 4 stages; returns the 5-level pyramid (depth_encoder.py:35-44).
         `ready_tag`: report gradient completion in two steps (layer4, then the rest) to the data-parallel hook.
@@ -265,9 +373,15 @@ class ResNet(nn.Module):
         if ready_tag:
             ops.grad_ready(ready_tag + ".lo")
         x = ops.affine(img, 1.0 / 0.225, -0.45 / 0.225)
-        c0 = conv_apply(self.conv1, x)
-        if not need_f0 and self.bn1.training and _STEM_FUSE and c0.t.shape[2] % 4 == 0 and c0.t.shape[3] % 4 == 0:
+        fz = frozen_of(self.conv1, self.bn1)
+        c0 = conv_apply(self.conv1, x) if fz is None else None
+        if fz is not None:                 # frozen inference: bn1 and the ReLU ride in the stem convolution; level 0 stays available
+            f0 = fz.apply(x, ACT_RELU)
+            feats = [f0]
+            x = ops.maxpool(f0, 3, 2, 1)
+        elif not need_f0 and self.bn1.training and _STEM_FUSE and c0.t.shape[2] % 4 == 0 and c0.t.shape[3] % 4 == 0:
             self.bn1._pending += n_updates * groups
+            self.bn1._updates += 1
             feats = [None]
             x = ops.bn_relu_maxpool_train(c0, P(self.bn1.weight), P(self.bn1.bias), self.bn1.running_mean, self.bn1.running_var,
                                           self.bn1.momentum, self.bn1.eps, n_updates, groups)
@@ -485,10 +599,18 @@ class Decoder(nn.Module):
         mods.append(Conv3x3(int(self.num_ch_dec[0]), num_class))
         self.decoder = nn.ModuleList(mods)
 
+    def _conv_bn_pairs(self):
+        d = self.decoder
+        return [(d[5 * s + o], d[5 * s + o + 1]) for s in range(5) for o in (0, 3)]
+
     def _fwd(self, x, n_updates=1):
         d = self.decoder
         for s in range(5):
             c0, b0, _, c1, b1 = d[5 * s], d[5 * s + 1], d[5 * s + 2], d[5 * s + 3], d[5 * s + 4]
+            f0, f1 = frozen_of(c0, b0), frozen_of(c1, b1)
+            if f0 is not None and f1 is not None:             # frozen inference: both BatchNorms (and the ReLU) ride in their convolutions
+                x = f1.apply(None, srcs=[(f0.apply(x, ACT_RELU), 1)])
+                continue
             x = bn_apply(b0, conv_apply(c0, x), relu=True, n_updates=n_updates)
             x = conv_apply(c1, None, srcs=[(x, 1)])          # nearest 2x upsample fused into the conv gather
             x = bn_apply(b1, x, n_updates=n_updates)

@@ -188,11 +188,14 @@ import numpy as np
 _JOB_DT = np.dtype([("w", "u8"), ("wp", "u8"), ("total", "i8"), ("begin", "i8"), ("mode", "i4"), ("p", "i4", (6,)),
                     ("pad", "i4")])
 _EPOCH = [0]
+_WRITES = [0]           # weights_changed() calls: what caches of parameter VALUES compare (modules.FrozenConvBN) -- the epoch also moves
+                        # when refresh_all merely notices a version sum that differs, e.g. because more layers were packed
 
 
 def weights_changed():
     """Tell the pack cache that parameter memory was rewritten behind autograd's back (optimizer kernels, .data edits)."""
     _EPOCH[0] += 1
+    _WRITES[0] += 1
 
 
 class _PackEntry:
@@ -245,6 +248,13 @@ class PackRegistry:
             del self.entries[key]
             self.table = None
 
+    def invalidate(self, p):
+        """The memory of parameter `p` was rewritten by a kernel (no version bump, no new epoch -- a folded weight re-folded in place,
+        modules.FrozenConvBN): its packs are re-made by the next convolution that uses them (_conv_call) or the next refresh_all."""
+        for e in self.entries.values():
+            if e.param is p:
+                e.epoch = -1
+
     def ensure_table(self):
         """Build the device job table of every live pack if it is missing (a host-to-device copy: CapturedStep calls this
         BEFORE it starts capturing, refresh_all inside the capture then only launches).  -> False when there is nothing to replay."""
@@ -277,7 +287,7 @@ class PackRegistry:
                 vs += p._version
         if vs != self.versions:
             if self.versions is not None:
-                weights_changed()
+                _EPOCH[0] += 1
             self.versions = vs
         ep = _EPOCH[0]
         stale = [e for e in self.entries.values() if e.epoch != ep and e.jobs is not None]
@@ -864,6 +874,22 @@ def add(a: Var, b: Var) -> Var:
         out.g = None
 
     _rec(out.rg, bwd)
+    return out
+
+
+def add_relu(a: Var, b: Var, relu=True, inplace=False) -> Var:
+    """relu(a + b) in one pass (jp_add_relu): the tail of a BasicBlock whose BatchNorms are folded into its convolutions (frozen
+    inference).  Forward-only.  `inplace`: the result overwrites a's tensor (the caller owns it).  The kernel reports max|out|: the
+    operand scale of the next convolution."""
+    if _TAPE is not None:
+        raise RuntimeError("ops.add_relu is forward-only (frozen inference): a tape is recording")
+    if a.t.shape != b.t.shape:
+        raise ValueError(f"add_relu: shapes differ ({tuple(a.t.shape)} vs {tuple(b.t.shape)})")
+    y = a.t if inplace else torch.empty_like(a.t)
+    slot = _out_slot(y.device)
+    call("jp_add_relu", a.t, b.t, y, y.numel(), int(bool(relu)), slot)
+    out = Var(y)
+    out.amax = slot
     return out
 
 

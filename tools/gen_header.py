@@ -74,6 +74,18 @@ GROUPS = [
      "pooled output + argmax byte in forward, the convolution-output gradient straight from the pooled gradient in backward.",
      ["jp_bn_ws_doubles", "jp_bn_train_fwd", "jp_bn_train_bwd", "jp_bn_eval_fwd", "jp_bn_relu_pool_fwd",
       "jp_bn_relu_pool_bwd_ws_doubles", "jp_bn_relu_pool_bwd"]),
+    ("Frozen inference (csrc/frozen.hip; model/modules.py FrozenConvBN, apis.freeze) -- an eval-mode BatchNorm2d behind a convolution ("
+     + R + "resnet.py:29-45,92; " + R + "layout_model.py:138-153) folded into that convolution, no counterpart in the reference.  "
+     "jp_bn_fold_conv: w (Cout, K) with K = Cin*KH*KW, conv_bias (Cout) or NULL (= 0); per output channel in float64 "
+     "s = gamma / sqrt(running_var + eps), w_out[c,:] = float(w[c,:] * s), bias_out[c] = float(beta + (conv_bias - running_mean) * s), "
+     "each operation rounded once and nothing clamped (negative, zero and tiny gamma come out as the formula says); one workgroup per "
+     "channel; w_out != w.  Run once per freeze, then the folded pair is jp_conv2d_fwd* with bias and act.  jp_add_relu: out = a + b, "
+     "then max(., 0) when relu != 0 -- the tail of a BasicBlock after folding (residual add + ReLU), one pass, 16-byte accesses when the "
+     "three pointers are 16-byte aligned and a scalar tail; out may be a (not b).  The ReLU is `r > 0 ? r : 0`, the result of "
+     "jp_bn_eval_fwd's fmaxf(r, 0) which it replaces: a NaN sum becomes 0 (torch.relu would keep the NaN) and -0.0 becomes +0.0; "
+     "with relu == 0 the sum is stored as it is, NaN included (max |out| ignores a NaN either way).  amax_out: optional magnitude slot that receives "
+     "max |out| (the convention of jp_sum_n amax_out above).",
+     ["jp_bn_fold_conv", "jp_add_relu"]),
     ("Pooling / resampling / elementwise — MaxPool2d " + R + "resnet.py:94, " + R + "layers.py:191, " + R + "layout_model.py:84; "
      "nearest upsample " + R + "layers.py:110; torch.cat; Dropout multiply " + R + "depth_decoder.py:52-53; F.interpolate bilinear "
      + R + "net.py:196,632,692 and area " + R + "net.py:762.",
@@ -176,8 +188,10 @@ GROUPS = [
      "(jp_color_jitter_op folds its gray sum with atomic adds).",
      ["jp_resample_h_u8", "jp_resample_v_u8", "jp_u8_to_tensor", "jp_color_jitter_op", "jp_topview_u8", "jp_resample_h_u8_flip",
       "jp_u8_to_tensor_flip", "jp_topview_u8_flip", "jp_color_jitter_batched_ws_doubles", "jp_color_jitter_batched"]),
-    ("Library plumbing.  jp_profile_*: opt-in per-kernel HIP-event timing of the implicit-GEMM launches on the streams they "
-     "are launched on (bench.py's roofline leg; never active in the train step).",
+    ("Library plumbing.  jp_profile_*: opt-in per-kernel HIP-event timing on the streams the kernels are launched on (bench.py's "
+     "roofline leg; never active in the train step).  Recorded are the implicit-GEMM launches (tag = the launch helper's "
+     "instantiation, flops = executed FLOPs of the GEMM) and two element-wise kernels of the eval-mode forward, jp_bn_eval_fwd "
+     "and jp_add_relu (tag = the entry point's name, flops = 0: they run no GEMM; tools/frozen_bench.py compares them).",
      ["jp_abi_version", "jp_last_error_string", "jp_set_last_error", "jp_profile_begin", "jp_profile_count", "jp_profile_end",
       "jp_profile_get"]),
 ]

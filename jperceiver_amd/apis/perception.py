@@ -3,6 +3,7 @@
     Perceiver(model).perceive(frames, prev)       -> Perception: raw disparity, metric depth at the output size, the
                                                      bird's-eye-view class map and the ego-motion of the pair
     Perceiver(model).perceive_video(frames)       -> VideoPerception: the same over a drive, plus the chained trajectory
+    Perceiver(model).stream(src_hw)               -> PerceptionStream (apis/stream.py): raw uint8 frames one by one, state kept on the device
     colorize_disp(disp, lut, q=0.95)              -> the script's `plt.imsave(..., cmap='magma', vmax=np.percentile(disp, 95))`
     layout_rgb(layout)                            -> the script's palette image of the class map
     quantiles(x, q)                               -> np.quantile(x, q, axis=1) by exact selection on the device
@@ -200,6 +201,12 @@ class Perceiver:
                 raise ValueError("prev must have the shape of frames")
             T = self.model.predict_poses({("color_aug", 0, 0): frames, ("color_aug", -1, 0): prev}, frame_ids=[0, -1])[("cam_T_cam", 0, -1)]
         return Perception(disp, depth, layout, T)
+
+    def stream(self, src_hw, **kw):
+        """A `PerceptionStream` (apis/stream.py) over this model with this Perceiver's output size and depth range: raw uint8
+        camera frames of src_hw = (h, w) pushed one by one."""
+        from .stream import PerceptionStream
+        return PerceptionStream(self.model, src_hw, **{**dict(out_size=self.out_size, min_depth=self.min_depth, max_depth=self.max_depth), **kw})
 
     @torch.no_grad()
     def perceive_video(self, frames, batch=8) -> VideoPerception:

@@ -1,0 +1,149 @@
+"""Streaming perception: one object that takes raw camera frames one by one and answers with depth, the bird's-eye-view class
+map, the ego-motion of the frame and the running trajectory -- what the reference's demo (scripts/eval_kitti_video.py:
+`transform()`, `predict()` and the chaining at :281-292) does per frame with host numpy, a kept `prev` image and a kept global
+pose, here on the device end to end:
+
+    s = PerceptionStream(model, src_hw=(375, 1242))        # or Perceiver(model).stream((375, 1242))
+    for frame in camera:                                    # (cameras, h, w, 3) uint8, host or device
+        f = s.push(frame)                                   # StreamFrame(index, disp, depth, layout, cam_T_cam, pose)
+    s.trajectory()                                          # (cameras, n, 12) float64, rows 0..2 of every global pose
+
+What one push runs, on the current stream:  DevicePreprocessor.resize_u8 (the Pillow-exact Lanczos resize + ToTensor)  ->  the
+model's eval forward (frozen by default, apis.freeze; Baseline.eval_branch: without the Softmax2d maps and the published extras
+nothing here reads)  ->  jp_stream_pose_pair (the frame resized to 192 x 640, paired with its predecessor out of a two-slot ring;
+with itself for the first frame, as the demo does)  ->  PoseEncoder, PoseDecoder, jp_pose_fwd(invert)  ->  disp_resize_depth,
+layout_classes  ->  jp_stream_traj_push (T_k = T_{k-1} @ cam_T_cam_k in float64, T_0 = I).  "Previous frame" and "trajectory
+row k" are decided by a frame counter in DEVICE memory: every launch of a push has the same arguments for every frame, nothing is
+copied back, and the host never reads the counter (it mirrors the count).  `push` never synchronises.  Against
+Perceiver.perceive(cur, prev) the previous frame is resized for the pose nets once instead of twice, and the results are the same
+bits.  Weights that change between pushes are picked up as by any eval forward (the frozen state's and the pack registry's host
+checks run in every push).
+
+THE RETURNED TENSORS ARE THE SESSION'S STATIC OUTPUT BUFFERS: they are valid until the next `push` (or `reset`), which
+overwrites them in place -- clone what has to live longer.
+
+Frames in pinned host memory are copied without blocking: the caller must leave that buffer untouched until the copy has run
+(an event recorded after `push`, or any later synchronisation, tells)."""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+import torch
+
+from .. import ops
+from ..datasets.preprocess import DevicePreprocessor
+from ..ops import Var
+
+_PH, _PW = 192, 640          # the pose nets' input (net.py:632)
+
+
+class StreamFrame(NamedTuple):
+    index: int                              # 0 for the first frame after construction / reset()
+    disp: torch.Tensor                      # (cameras,1,h,w)   the network's ("disp", 0, 0) head, in [0,1]
+    depth: torch.Tensor                     # (cameras,1,OH,OW) metres
+    layout: torch.Tensor                    # (cameras,occ,occ) uint8: 0 background, 1 road, 2 car
+    cam_T_cam: Optional[torch.Tensor]       # (cameras,4,4) transform for frame -1; None for index 0
+    pose: torch.Tensor                      # (cameras,4,4) float64 global pose: I for index 0, then pose @ cam_T_cam
+
+
+class PerceptionStream:
+    """See the module docstring.  model: an eval-mode `Baseline` on the GPU that holds a checkpoint; src_hw: (h, w) of the camera
+    frames; out_size: (OH, OW) of the depth maps (default: the network's resolution); min_depth / max_depth default to
+    model.opt's; capacity: trajectory rows kept per camera (later frames still update `pose`)."""
+
+    def __init__(self, model, src_hw, cameras=1, out_size=None, min_depth=None, max_depth=None, capacity=4096, frozen=True):
+        if model.training:
+            raise RuntimeError("PerceptionStream expects an eval-mode model (call .eval(): BatchNorm must use running stats)")
+        p = next(model.parameters())
+        if not p.is_cuda:
+            raise RuntimeError("PerceptionStream runs HIP kernels: move the model to the GPU first (there is no CPU path)")
+        h, w = int(src_hw[0]), int(src_hw[1])
+        self.cameras, self.capacity = int(cameras), int(capacity)
+        if h < 1 or w < 1 or self.cameras < 1 or self.capacity < 1:
+            raise ValueError("src_hw, cameras and capacity must be positive")
+        if frozen:
+            from .inference import freeze
+            freeze(model)
+        self.model, self.dev, self.src_hw = model, p.device, (h, w)
+        self.net_hw = (int(model.opt.height), int(model.opt.width))
+        self.out_size = self.net_hw if out_size is None else (int(out_size[0]), int(out_size[1]))
+        self.min_depth = float(model.opt.min_depth if min_depth is None else min_depth)
+        self.max_depth = float(model.opt.max_depth if max_depth is None else max_depth)
+        B, dev = self.cameras, self.dev
+        self._pre = DevicePreprocessor(self.net_hw[0], self.net_hw[1], dev)
+        self._in = torch.zeros((B, h, w, 3), device=dev, dtype=torch.uint8)
+        self._ring = torch.zeros((2, B, 3, _PH, _PW), device=dev)
+        self._count = torch.zeros(1, device=dev, dtype=torch.int32)
+        self._pose = torch.zeros((B, 16), device=dev, dtype=torch.float64)
+        self._traj = torch.zeros((B, self.capacity, 12), device=dev, dtype=torch.float64)
+        self._T = torch.zeros((B, 4, 4), device=dev)
+        self._K = torch.eye(4, device=dev).repeat(B, 1, 1)            # only T is read (P = K @ T is jp_pose_fwd's by-product)
+        self._P = torch.empty((B, 3, 4), device=dev)
+        self._depth = torch.empty((B, 1) + self.out_size, device=dev)
+        self._disp = self._layout = None                              # shaped by the first pass
+        self._n = 0
+
+    # ---------------------------------------------------------------------------------------- state
+    def reset(self):
+        """Forget the stream: the next frame is frame 0 again (paired with itself, pose = I, trajectory row 0)."""
+        for t in (self._count, self._ring, self._pose, self._traj, self._T):
+            t.zero_()
+        self._n = 0
+
+    def trajectory(self):
+        """(cameras, n, 12) float64 device tensor, a copy: rows 0..2 of the global pose of every frame pushed so far (at most
+        `capacity` of them), T_0 = I and T_k = T_{k-1} @ cam_T_cam_k."""
+        return self._traj[:, :min(self._n, self.capacity)].clone()
+
+    def _check_frames(self, frames):
+        if not (isinstance(frames, torch.Tensor) and frames.dtype == torch.uint8):
+            raise TypeError("frames must be a uint8 tensor (raw camera frames; the session resizes and scales them itself)")
+        want = (self.cameras,) + self.src_hw + (3,)
+        if tuple(frames.shape) != want:
+            raise ValueError(f"frames must have shape (cameras, h, w, 3) = {want}, got {tuple(frames.shape)}")
+        if frames.is_cuda and frames.device != self.dev:
+            raise ValueError(f"frames live on {frames.device}, the session on {self.dev}")
+
+    # ---------------------------------------------------------------------------------------- one frame
+    def _body(self):
+        """The launches of one push, on the current stream."""
+        m, B, dev = self.model, self.cameras, self.dev
+        H, W = self.net_hw
+        img = self._pre.resize_u8(self._in, H, W)
+        x = Var(img)
+        feats = m.eval_branch("depth_encoder", x)
+        disp = m.eval_branch("depth_decoder", feats)
+        if self._disp is None:
+            self._disp = torch.empty_like(disp)
+        h, w = disp.shape[2:]
+        ops.call("jp_axpby", disp, None, self._disp, disp.numel(), 1.0, 0.0)
+        ops.call("jp_disp_resize_depth", self._disp, self._depth, None, B, h, w, self.out_size[0], self.out_size[1],
+                 self.min_depth, self.max_depth)
+        road, car = m.eval_branch("layout_heads", m.eval_branch("layout_encoder", x), feats[-1])
+        h, w = road.shape[2:]
+        if self._layout is None:
+            self._layout = torch.empty((B, h, w), device=dev, dtype=torch.uint8)
+        ops.call("jp_layout_classes_u8", road, car, self._layout, None, B, h * w)
+        pair = torch.empty((B, 6, _PH, _PW), device=dev)
+        # (no magnitude slot: the pose encoder normalises the pair into a new tensor first (ops.affine), and the stem convolution
+        # reduces the magnitude of THAT input itself where its kernel reads one -- nothing reads max |pair|)
+        ops.call("jp_stream_pose_pair", img, self._ring, self._count, pair, None, B, H, W)
+        aa, tr = m.eval_branch("pose", Var(pair))
+        ops.call("jp_pose_fwd", aa.t, tr.t, self._K, self._T, self._P, B, 1)
+        ops.call("jp_stream_traj_push", self._T, self._pose, self._traj, self._count, B, self.capacity)
+
+    @torch.no_grad()
+    def push(self, frames_u8) -> StreamFrame:
+        """frames_u8: (cameras, h, w, 3) uint8, on the session's device or on the host (pinned host memory is copied without
+        blocking and must stay untouched until that copy has run).  Enqueues the frame's work and returns the static output
+        buffers; never waits for the device."""
+        if self.model.training:
+            raise RuntimeError("PerceptionStream expects an eval-mode model")
+        self._check_frames(frames_u8)
+        with torch.cuda.device(self.dev):
+            self._in.copy_(frames_u8, non_blocking=True)
+            ops.PackRegistry.of(self.dev).refresh_all()
+            self._body()
+        k = self._n
+        self._n += 1
+        return StreamFrame(k, self._disp, self._depth, self._layout, self._T if k > 0 else None, self._pose.view(-1, 4, 4))

@@ -4,6 +4,7 @@
 // area resizes (net.py:632,692,762).  NCHW fp32; one thread per output element, lanes along W so
 // every wave touches contiguous 256-B segments.
 #include "jp_common.h"
+#include "bilinear.h"
 #include <algorithm>
 
 namespace {
@@ -754,15 +755,7 @@ __global__ __launch_bounds__(TPB) void mul_bcast_c_bwd_s_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------ bilinear resize, align_corners=False
-__device__ __forceinline__ void bil_src(int o, float scale, int in, int& i0, int& i1, float& w1) {
-    float src = ((float)o + 0.5f) * scale - 0.5f;   // PyTorch area_pixel_compute_source_index
-    if (src < 0.f) src = 0.f;
-    i0 = (int)src;
-    if (i0 > in - 1) i0 = in - 1;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    w1 = src - (float)i0;
-}
-
+// (the sampling rule, bil_src / bil_sample, lives in bilinear.h: stream.hip resizes with the same bits)
 __global__ __launch_bounds__(TPB) void bilinear_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                            long total, int H, int W, int OH, int OW, float sy,
                                                            float sx) {
@@ -771,13 +764,7 @@ __global__ __launch_bounds__(TPB) void bilinear_fwd_kernel(const float* __restri
         const long t = o / OW;
         const int oy = (int)(t % OH);
         const long nc = t / OH;
-        int y0, y1, x0, x1;
-        float wy, wx;
-        bil_src(oy, sy, H, y0, y1, wy);
-        bil_src(ox, sx, W, x0, x1, wx);
-        const float* xp = x + nc * H * W;
-        const float a = xp[y0 * W + x0], b = xp[y0 * W + x1], c = xp[y1 * W + x0], d = xp[y1 * W + x1];
-        y[o] = (1.f - wy) * ((1.f - wx) * a + wx * b) + wy * ((1.f - wx) * c + wx * d);
+        y[o] = bil_sample(x + nc * H * W, oy, ox, H, W, sy, sx);
     }
 }
 

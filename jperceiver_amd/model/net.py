@@ -187,6 +187,32 @@ class Baseline(nn.Module):
         out["origin_features"] = F.t
         return out
 
+    def eval_branch(self, name, *args):
+        """One branch of the eval forward for a caller that schedules the branches itself (apis.PerceptionStream puts them on
+        streams of its own inside one captured graph).  The launches are those of `_forward_eval` / `predict_poses`, branch by
+        branch and in their order, without the Softmax2d probability maps and the `_publish_head` extras, which are by-products:
+          "depth_encoder", img Var         -> DepthEncoder pyramid
+          "depth_decoder", pyramid         -> ("disp", 0, 0) tensor
+          "layout_encoder", img Var        -> LayoutEncoder pyramid
+          "layout_heads", F, f4            -> (road logits, car logits): `topview`, `topviewB`; f4 = the depth pyramid's last level
+          "pose", pair Var (B,6,192,640)   -> (axisangle, translation) Vars (B,3) of the pair [frame -1 | frame 0]
+        Eval mode only; nothing is recorded; the caller refreshes the pack registry (ops.PackRegistry.refresh_all)."""
+        if self.training:
+            raise RuntimeError("eval_branch expects an eval-mode model (call .eval(): BatchNorm must use running stats)")
+        with recording(None):
+            if name == "depth_encoder":
+                return self.DepthEncoder._fwd(args[0])
+            if name == "depth_decoder":
+                return self.DepthDecoder._fwd(args[0])[("disp", 0, 0)].t
+            if name == "layout_encoder":
+                return self.LayoutEncoder._fwd(args[0])
+            if name == "layout_heads":
+                F, f4 = args
+                return tuple(self._layout_head(sfx, F, f4, 1)["top"].t for sfx in ("", "B"))
+            if name == "pose":
+                return _split6(self.PoseDecoder._fwd(self.PoseEncoder._fwd(args[0])))
+        raise ValueError(f"eval_branch: unknown branch {name!r}")
+
     # ------------------------------------------------------------------ eval-mode poses (net.py:630-642)
     @torch.no_grad()
     def predict_poses(self, inputs, frame_ids=None):

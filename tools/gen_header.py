@@ -151,6 +151,23 @@ GROUPS = [
      "road and the car head (B, 2, HW; strictly-greater, ties -> 0; car_logits nullable) -> cls (B, HW) bytes 0 / 1 road / 2 car "
      "and (nullable) rgb (B, HW, 3) with the palette (0,0,0) / (255,255,255) / (0,0,255) (:157-161,195-218).",
      ["jp_disp_resize_depth", "jp_quantiles_ws_bytes", "jp_quantiles", "jp_colorize_u8", "jp_layout_classes_u8"]),
+    ("Streaming perception (csrc/stream.hip; apis/stream.py PerceptionStream) -- the per-frame state of a streaming session, kept in device "
+     "memory, no counterpart in the reference (scripts/eval_kitti_video.py keeps the previous frame and the global "
+     "pose in host variables, :281-292).  Every launch of a frame has the same arguments as the last frame's (what a captured graph would need): both entry points read the number of frames pushed "
+     "so far, n, from `count`: ONE int32 in device memory.  Ring, pose, trajectory and counter are the caller's buffers (the library "
+     "keeps no state).  jp_stream_pose_pair: frame (B,3,H,W) is resized to 192 x 640 with the arithmetic of jp_bilinear_fwd "
+     "(half-pixel, align_corners=False; bit-equal to it) into ring[n & 1] (ring: (2,B,3,192,640)) and into pair[:,3:6] (pair: "
+     "(B,6,192,640)); pair[:,0:3] = ring[(n & 1) ^ 1], the frame of the call before, or the new frame itself when n == 0 (the demo "
+     "pairs its first frame with itself) -- Baseline.predict_poses' [pf[-1], pf[0]] of frame_ids = [0, -1] in one launch, the previous "
+     "frame resized only once.  amax_out: optional magnitude slot that receives max |pair| (the convention of jp_add_relu amax_out "
+     "above).  count is only read.  jp_stream_traj_push: T (B,4,4) float, the cam_T_cam of frame -1 as jp_pose_fwd writes it; pose "
+     "(B,16) double, the current global pose (row-major 4 x 4); traj (B,capacity,12) double.  n == 0: pose = I whatever T holds; "
+     "else pose = pose @ double(T) (eval_kitti_video.py:292), every element ((a0 b0 + a1 b1) + a2 b2) + a3 b3 in float64 with each "
+     "product and sum rounded once (no fma), the whole old pose read before any of it is written.  Rows 0..2 of the new pose go to "
+     "traj[:, n] when n < capacity (later frames leave the trajectory alone; pose and count go on).  One thread stores count = n + 1 "
+     "after every camera is done: jp_stream_pose_pair of a frame must be enqueued BEFORE its jp_stream_traj_push (one stream, or an "
+     "event in between).  One workgroup, no atomics.",
+     ["jp_stream_pose_pair", "jp_stream_traj_push"]),
     ("KITTI odometry evaluation (csrc/odometry.hip; core/evaluation.py::eval_odometry, apis/inference.py) — the pose chaining of "
      "scripts/draw_odometry.py:62-76 and the numpy toolkit behind the paper's t_err / r_err (mono/tools/kitti_evaluation_toolkit.py:"
      "109-201, mono/tools/geometry.py:20-67, scripts/plot_kitti.py:15-97,223-243).  All arithmetic is double, no atomics: every sum "

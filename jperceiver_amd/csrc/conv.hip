@@ -2349,6 +2349,32 @@ template <bool REFLECT, bool REV, class E, int TAPS>
 void launch_p9s(const float* wp, const float* x, E e, int rows, int red, int N, int H, int W, const JpCall& st, int mt_off, int bmt) {
     constexpr int KGS = TAPS == 9 ? 1 : 2;
     const int NST = red / (16 * KGS);
+    // ---- the kernel and its grid, chosen ONCE: the statistics partials, the profiler tag and the launch below all follow this choice.
+    // M tile bmt = 64 / 256 / 128 rows <-> WM x WN = 1x4 / 4x2 / 2x2 waves; a wave owns NJ = 2 pixel rows, 4 in the wide tiles (3x3 layers
+    // only, and only where they keep every CU busy: JP_P9_TILE above)
+    enum Variant { WIDE_1x4, WIDE_4x2, WIDE_2x2, NARROW_1x4, NARROW_4x2, NARROW_2x2, P1L };
+    // variant = (wide or narrow block) + shape, shape = 0 / 1 / 2 for the 1x4 / 4x2 / 2x2 wave grids: both blocks list the shapes in that order
+    static_assert(WIDE_4x2 == WIDE_1x4 + 1 && WIDE_2x2 == WIDE_1x4 + 2 && NARROW_4x2 == NARROW_1x4 + 1 && NARROW_2x2 == NARROW_1x4 + 2,
+                  "the variant is computed as block + shape");
+    const int shape = bmt == 64 ? 0 : (bmt == 256 ? 1 : 2), WN = bmt == 64 ? 4 : 2;
+    const int gy = bmt == 64 ? 1 : jp_cdiv(rows, bmt == 256 ? 256 : 128);
+    bool wide = false;
+    if (TAPS == 9) {
+        const int mode = p9_tile(), min_mode[3] = {3, 1, 2};        // least JP_P9_TILE that turns on wide tiles, by shape (1x4, 4x2, 2x2)
+        wide = mode >= min_mode[shape] && H % (4 * WN) == 0 && (long)N * (H / (4 * WN)) * (W / 32) * gy >= 256;
+    }
+    int variant = (wide ? WIDE_1x4 : NARROW_1x4) + shape;
+    dim3 grid(N * (H / ((wide ? 4 : 2) * WN)) * (W / 32), gy, 1);
+    const dim3 block(bmt == 256 ? 512 : 256);
+#if JP_NS == 3
+    const long p1l_tiles = (long)N * (H / 4) * (W / 32), p1l_xb = (long)N * red * H * W * 4;
+    const int p1l_tpw = jp_cdiv(p1l_tiles, jp_num_cus());
+    if (TAPS == 1 && bmt == 256 && mt_off == 0 && p1l_enabled() && rows % 256 == 0 && red % 128 == 0 && H % 4 == 0 && W % 32 == 0 &&
+        p1l_xb < (1L << 31) && p1l_tiles >= 8L * jp_num_cus()) {     // (4 tiles per workgroup, the @128^2 layers: no gain over the patch kernel, profiles/r05_p1l_conv_bench.log)
+        variant = P1L;
+        grid = dim3(jp_cdiv(p1l_tiles, p1l_tpw), rows / 256, 1);
+    }
+#endif
     const unsigned* wq = reinterpret_cast<const unsigned*>(wp);
     const float* xam = JP_NS == 2 ? jp_amax_of(x, (long)N * red * H * W, st) : nullptr;
     if constexpr (JP_NS == 2 && jp_has_amax<E>::value) e.amax = jp_take_amax_out(st);       // (every kernel below reports it)
@@ -2357,65 +2383,34 @@ void launch_p9s(const float* wp, const float* x, E e, int rows, int red, int N, 
         // sums over its pixels are plain register adds + one cross-half shuffle); partials per channel = pixel tiles x pixel-row waves
         e.stats = nullptr;
         if (TAPS == 9 && bmt != 256 && mt_off == 0 && st.ax && st.ax->stats) {
-            const int mode = p9_tile();
-            long tiles;
-            if (bmt == 64) tiles = (mode >= 3 && H % 16 == 0 && (long)N * (H / 16) * (W / 32) >= 256) ? (long)N * (H / 16) * (W / 32) : (long)N * (H / 8) * (W / 32);
-            else tiles = (mode >= 2 && H % 8 == 0 && (long)N * (H / 8) * (W / 32) * jp_cdiv(rows, bmt) >= 256) ? (long)N * (H / 8) * (W / 32) : (long)N * (H / 4) * (W / 32);
             e.stats = st.ax->stats;
-            st.ax->stats_parts = (int)(tiles * (bmt == 64 ? 4 : 2));
+            st.ax->stats_parts = (int)(grid.x * WN);
         }
     }
+    // executed FLOPs: JP_NPROD 16-bit MFMA products per fp32 product
+    const double flops = JP_NPROD * 2.0 * rows * (double)N * H * W * TAPS * red;
+    auto go = [&](const char* tag, auto kernel) {
+        jp_prof_before(tag, flops, st);
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, wq, x, e, rows, red, NST, H, W, mt_off, xam);
+        jp_prof_after(st);
+    };
+    switch (variant) {
+        case WIDE_1x4: if constexpr (TAPS == 9) go(p9sw_tag<1, 4, REFLECT, REV, E, TAPS>(), jp_igemm_p9s_wide_kernel<1, 4, REFLECT, REV, E, TAPS, KGS>); break;
+        case WIDE_4x2: if constexpr (TAPS == 9) go(p9sw_tag<4, 2, REFLECT, REV, E, TAPS>(), jp_igemm_p9s_wide_kernel<4, 2, REFLECT, REV, E, TAPS, KGS>); break;
+        case WIDE_2x2: if constexpr (TAPS == 9) go(p9sw_tag<2, 2, REFLECT, REV, E, TAPS>(), jp_igemm_p9s_wide_kernel<2, 2, REFLECT, REV, E, TAPS, KGS>); break;
+        case NARROW_1x4: go(p9s_tag<1, 4, REFLECT, REV, E, TAPS>(), jp_igemm_p9s_kernel<1, 4, 2, REFLECT, REV, E, TAPS, KGS>); break;
+        case NARROW_4x2: go(p9s_tag<4, 2, REFLECT, REV, E, TAPS>(), jp_igemm_p9s_kernel<4, 2, 2, REFLECT, REV, E, TAPS, KGS>); break;
+        case NARROW_2x2: go(p9s_tag<2, 2, REFLECT, REV, E, TAPS>(), jp_igemm_p9s_kernel<2, 2, 2, REFLECT, REV, E, TAPS, KGS>); break;
+        case P1L:
 #if JP_NS == 3
-    if constexpr (TAPS == 1) {
-        const long ntiles = (long)N * (H / 4) * (W / 32), xb = (long)N * red * H * W * 4;
-        if (bmt == 256 && mt_off == 0 && p1l_enabled() && rows % 256 == 0 && red % 128 == 0 && H % 4 == 0 && W % 32 == 0 && xb < (1L << 31) &&
-            ntiles >= 8L * jp_num_cus()) {     // (4 tiles per workgroup, the @128^2 layers: no gain over the patch kernel, profiles/r05_p1l_conv_bench.log)
-            const int G = jp_num_cus(), tpw = jp_cdiv(ntiles, G);
-            jp_prof_before(p1l_tag<E>(), JP_NPROD * 2.0 * rows * (double)N * H * W * red, st);
-            hipLaunchKernelGGL((jp_conv1x1_p1l_kernel<E>), dim3(jp_cdiv(ntiles, tpw), rows / 256, 1), dim3(512), 0, st, wq, x, e, rows, red, NST,
-                                   H, W, (int)ntiles, tpw, (int)xb);
-            jp_prof_after(st);
-            return;
-        }
-    }
+            if constexpr (TAPS == 1) {
+                jp_prof_before(p1l_tag<E>(), flops, st);
+                hipLaunchKernelGGL((jp_conv1x1_p1l_kernel<E>), grid, block, 0, st, wq, x, e, rows, red, NST, H, W, (int)p1l_tiles, p1l_tpw, (int)p1l_xb);
+                jp_prof_after(st);
+            }
 #endif
-    if constexpr (TAPS == 9) {
-        // wide tiles (8 rows x 32 columns per workgroup, NJ = 4): only where they keep every CU busy (3x3 layers only)
-        const int mode = p9_tile();
-        if (TAPS == 9 && mode >= 3 && bmt == 64 && H % 16 == 0 && (long)N * (H / 16) * (W / 32) >= 256) {
-            jp_prof_before(p9sw_tag<1, 4, REFLECT, REV, E, TAPS>(), JP_NPROD * 2.0 * rows * (double)N * H * W * TAPS * red, st);
-            hipLaunchKernelGGL((jp_igemm_p9s_wide_kernel<1, 4, REFLECT, REV, E, TAPS, KGS>), dim3(N * (H / 16) * (W / 32), 1, 1), dim3(256), 0,
-                               st, wq, x, e, rows, red, NST, H, W, mt_off, xam);
-            jp_prof_after(st);
-            return;
-        }
-        const bool want = (mode >= 1 && bmt == 256) || (mode >= 2 && bmt == 128);
-        if (want && H % 8 == 0 && (long)N * (H / 8) * (W / 32) * jp_cdiv(rows, bmt) >= 256) {
-            jp_prof_before(bmt == 256 ? p9sw_tag<4, 2, REFLECT, REV, E, TAPS>() : p9sw_tag<2, 2, REFLECT, REV, E, TAPS>(),
-                           JP_NPROD * 2.0 * rows * (double)N * H * W * TAPS * red, st);
-            dim3 grid(N * (H / 8) * (W / 32), jp_cdiv(rows, bmt), 1);
-            if (bmt == 256)
-                hipLaunchKernelGGL((jp_igemm_p9s_wide_kernel<4, 2, REFLECT, REV, E, TAPS, KGS>), grid, dim3(512), 0, st, wq, x, e, rows, red, NST, H, W, mt_off, xam);
-            else
-                hipLaunchKernelGGL((jp_igemm_p9s_wide_kernel<2, 2, REFLECT, REV, E, TAPS, KGS>), grid, dim3(256), 0, st, wq, x, e, rows, red, NST, H, W, mt_off, xam);
-            jp_prof_after(st);
-            return;
-        }
+            break;
     }
-    // executed FLOPs: 6 bf16 MFMA products per fp32 product
-    jp_prof_before(bmt == 64 ? p9s_tag<1, 4, REFLECT, REV, E, TAPS>() : (bmt == 256 ? p9s_tag<4, 2, REFLECT, REV, E, TAPS>() : p9s_tag<2, 2, REFLECT, REV, E, TAPS>()),
-                   JP_NPROD * 2.0 * rows * (double)N * H * W * TAPS * red, st);
-    if (bmt == 64) {
-        dim3 grid(N * (H / 8) * (W / 32), 1, 1);
-        hipLaunchKernelGGL((jp_igemm_p9s_kernel<1, 4, 2, REFLECT, REV, E, TAPS, KGS>), grid, dim3(256), 0, st, wq, x, e, rows, red, NST, H, W, mt_off, xam);
-    } else if (bmt == 256) {
-        dim3 grid(N * (H / 4) * (W / 32), jp_cdiv(rows, 256), 1);
-        hipLaunchKernelGGL((jp_igemm_p9s_kernel<4, 2, 2, REFLECT, REV, E, TAPS, KGS>), grid, dim3(512), 0, st, wq, x, e, rows, red, NST, H, W, mt_off, xam);
-    } else {
-        dim3 grid(N * (H / 4) * (W / 32), jp_cdiv(rows, 128), 1);
-        hipLaunchKernelGGL((jp_igemm_p9s_kernel<2, 2, 2, REFLECT, REV, E, TAPS, KGS>), grid, dim3(256), 0, st, wq, x, e, rows, red, NST, H, W, mt_off, xam);
-    }
-    jp_prof_after(st);
 }
 // 1x1 stride-2 (ResNet downsample branches) on the same tiles: forward = P9S with a stride-2 staging gather (igemm_p9s.h, XS = 2);
 // dgrad = the stride-1 kernel over the half-resolution grid with a scattering epilogue (DgradS2PointEpi)

@@ -43,6 +43,44 @@ template <class L> struct jp_has_split<L, std::void_t<decltype(L::SPLIT)>> : std
 
 typedef float jp_f32x16 __attribute__((ext_vector_type(16)));
 
+// XCD-aware tile order.  Workgroups are dealt round-robin to the 8 XCDs in dispatch order (x fastest), each with
+// its own 4 MiB L2.  Remap (blockIdx.x, blockIdx.y) -> (M tile mt, N tile nt) so that (a) every XCD owns a contiguous
+// band of N tiles -- vertically adjacent pixel tiles, which share two of their three input rows, then hit the same L2
+// instead of each pulling the rows over the fabric -- and (b) the gridDim.y M-tiles of one N-tile are consecutive
+// dispatches on that XCD and share the gathered B operand.
+struct jp_tile { int mt, nt, zs; };      // (M tile, N tile, K slice) of a workgroup
+__device__ __forceinline__ jp_tile jp_xcd_tile() {
+    const int gx = gridDim.x, gy = gridDim.y, G = gx & ~7;
+    const int L = blockIdx.x + blockIdx.y * gx;
+    if (L < G * gy) {
+        const int j = L >> 3;
+        return {j % gy, (L & 7) * (G >> 3) + j / gy, 0};
+    }
+    const int i = L - G * gy;
+    return {i % gy, G + i / gy, 0};
+}
+// Split-K launches (K slices over gridDim.z): every XCD owns whole K slices -- all (m, n) tiles of a slice read the same
+// pixel range of both operands in lock-step, so they share it through one L2 instead of 8.
+__device__ __forceinline__ jp_tile jp_xcd_tile_splitk() {
+    const int gx = gridDim.x, gy = gridDim.y, T = gx * gy, SG = gridDim.z & ~7;
+    const int L3 = blockIdx.x + blockIdx.y * gx + blockIdx.z * T;
+    int tile, zs;
+    if (L3 < SG * T) {
+        const int idx = L3 >> 3;
+        zs = (idx / T) * 8 + (L3 & 7);
+        tile = idx % T;
+    } else {
+        const int r = L3 - SG * T;
+        zs = SG + r / T;
+        tile = r % T;
+    }
+    return {tile % gy, tile / gy, zs};
+}
+
+// C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).  Row of register r of 32-row block i
+// of a wave whose rows start at `base`, for the lane half lhi = lane >> 5.
+__device__ __forceinline__ int jp_cd_row(int base, int i, int r, int lhi) { return base + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi; }
+
 template <int WM, int WN, int KC, class ALoad, class BLoad, class Epi, bool DB = false, bool IL = false>
 __global__ __launch_bounds__(64 * WM * WN) void jp_igemm_kernel(ALoad al, BLoad bl, Epi epi, int M, int N, int K,
                                                                int k_per_split) {
@@ -59,13 +97,9 @@ __global__ __launch_bounds__(64 * WM * WN) void jp_igemm_kernel(ALoad al, BLoad 
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    // XCD-aware tile order.  Workgroups are dealt round-robin to the 8 XCDs in dispatch order (x fastest), each with
-    // its own 4 MiB L2.  Remap so that (a) every XCD owns a contiguous band of N tiles -- vertically adjacent pixel
-    // tiles, which share two of their three input rows, then hit the same L2 instead of each pulling the rows over
-    // the fabric -- and (b) the gridDim.y M-tiles of one N-tile are consecutive dispatches on that XCD and share
-    // the gathered B operand.
-    // (c) split-K launches (gridDim.z > 1): every XCD owns whole K slices -- all (m, n) tiles of a slice read the same
-    // pixel range of both operands in lock-step, so they share it through one L2 instead of 8.
+    // the same mapping as jp_xcd_tile() / jp_xcd_tile_splitk() (gridDim.z > 1), kept as one block that shares L: routed through the two
+    // helpers, two instantiations of this kernel allocate one more SGPR.  An edit to the mapping here must be mirrored in the helpers and
+    // the other way round -- nothing else holds the two together.
     int mt = blockIdx.y, nt = blockIdx.x, zs = blockIdx.z;
     {
         const int gx = gridDim.x, gy = gridDim.y;
@@ -182,7 +216,7 @@ __global__ __launch_bounds__(64 * WM * WN) void jp_igemm_kernel(ALoad al, BLoad 
         }
     };
 
-    jp_f32x16 acc[2][2];
+    jp_f32x16 acc[2][2];       // (cleared element by element: `= {}` gives this kernel another instruction order)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -289,7 +323,6 @@ __global__ __launch_bounds__(64 * WM * WN) void jp_igemm_kernel(ALoad al, BLoad 
         }
     }
 
-    // C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int n = n0 + wn * 64 + j * 32 + l31;
@@ -299,7 +332,7 @@ __global__ __launch_bounds__(64 * WM * WN) void jp_igemm_kernel(ALoad al, BLoad 
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                const int m = jp_cd_row(m0 + wm * 64, i, r, lhi);
                 if (m < M) {
                     if constexpr (jp_epi_wants_slice<Epi>::value) epi.put(se, m, acc[i][j][r], zs);
                     else epi.put(se, m, acc[i][j][r]);
@@ -332,20 +365,8 @@ __global__ __launch_bounds__(64 * WM * WN) void jp_igemm_r3_kernel(ALoad al, BLo
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    int mt, nt;
-    {   // XCD band order, see jp_igemm_kernel
-        const int gx = gridDim.x, gy = gridDim.y, G = gx & ~7;
-        const int L = blockIdx.x + blockIdx.y * gx;
-        if (L < G * gy) {
-            const int j = L >> 3;
-            mt = j % gy;
-            nt = (L & 7) * (G >> 3) + j / gy;
-        } else {
-            const int i = L - G * gy;
-            mt = i % gy;
-            nt = G + i / gy;
-        }
-    }
+    const jp_tile tile = jp_xcd_tile();
+    const int mt = tile.mt, nt = tile.nt;
     const int m0 = mt * BM, n0 = nt * BN;
     const int a_fix_l = t % KC, a_var_l = t / KC;
     const int b_fix_l = t % BN, b_var_l = __builtin_amdgcn_readfirstlane(t / BN);
@@ -374,13 +395,7 @@ __global__ __launch_bounds__(64 * WM * WN) void jp_igemm_r3_kernel(ALoad al, BLo
             if (wave == 0) Bs[(lane >> 1) * LDB + ((lane & 1) ? BN + 1 : 0)] = rh;
         }
     };
-    jp_f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    jp_f32x16 acc[2][2] = {};
     const int l31 = lane & 31, lhi = lane >> 5;
     const float* ap = As + lhi * LDA + wm * 64 + l31;
     const float* bp = Bs + lhi * LDB + wn * 64 + l31;
@@ -416,7 +431,7 @@ __global__ __launch_bounds__(64 * WM * WN) void jp_igemm_r3_kernel(ALoad al, BLo
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                const int m = jp_cd_row(m0 + wm * 64, i, r, lhi);
                 if (m < M) epi.put(se, m, acc[i][j][r]);
             }
         }

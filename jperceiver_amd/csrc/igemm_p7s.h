@@ -18,13 +18,9 @@ template <int CIN, class Epi>
 __global__ __launch_bounds__(256, P7S_OCC) void jp_igemm_p7s_kernel(const unsigned* __restrict__ wp, const float* __restrict__ x, Epi epi,
                                                               int M, int OH, int OW, int ntiles, const float* __restrict__ xam) {
     constexpr int NS = JP_NS;
-    float xsc = 1.f, osc = 1.f;
-    if constexpr (NS == 2) {    // operand scales, see jp_igemm_p9s_body (the pack's header: PACK_SPLIT7)
-        const int kx = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(xam)));
-        xsc = jp_exp2i(kx);
-        osc = jp_exp2i(-kx) * __uint_as_float(__builtin_amdgcn_readfirstlane(wp[1]));
-        wp += JP_PACK_HDR;
-    }
+    const jp_scales sc = jp_operand_scales(wp, xam);     // (the pack's header: PACK_SPLIT7)
+    const float xsc = sc.xsc, osc = sc.osc;
+    wp = sc.wp;
     constexpr int NT = 256, NJ = 2, TR = 8;
     constexpr int STEPS = 4 * CIN;                                 // two of the 8 (padded) tap rows of a channel per step
     constexpr int PRW = 2 * TR + 6, PDW = 35, PITCH = 36;          // patch rows per channel, dwords per row, row pitch (dwords)
@@ -97,13 +93,7 @@ __global__ __launch_bounds__(256, P7S_OCC) void jp_igemm_p7s_kernel(const unsign
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned*>(wp), 0, (STEPS + 1) * SBYTES, 0x00020000);
     const int avo = (lhi * 64 + l31) * 16;
     jp_u32x4 ra[2][2][NS];
-    auto aload = [&](int slot, int step) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-                ra[slot][i][s] = __builtin_amdgcn_raw_buffer_load_b128(wrs, avo + i * 512 + s * (2 * 64 * 16), step * SBYTES, 0);
-    };
+    auto aload = [&](int slot, int step) { jp_weight_step_load<64>(wrs, avo, step * SBYTES, ra[slot]); };
     // ---- B: step u = (channel c = u / 4, tap rows ky = 2*(u % 4) + lhi); LDS dword of that patch row for output row j of this wave:
     // (c*PRW + 2*(2wn + j) + ky) * PITCH + l31 -- one lane base, everything else compile-time
     const unsigned* bpl = patch + (4 * wn + lhi) * PITCH + l31;
@@ -122,13 +112,7 @@ __global__ __launch_bounds__(256, P7S_OCC) void jp_igemm_p7s_kernel(const unsign
     // one tile per workgroup (co-resident workgroups hide each other's staging; a persistent tile loop made the compiler hoist
     // the epilogue's 32 row offsets across it and spill)
     const int T = blockIdx.x;
-    jp_f32x16 acc[2][NJ];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    jp_f32x16 acc[2][NJ] = {};
     aload(0, 0);
     gload(T);
     lstore();
@@ -147,7 +131,6 @@ __global__ __launch_bounds__(256, P7S_OCC) void jp_igemm_p7s_kernel(const unsign
     }
     int img, i0, j0;
     tile_org(T, img, i0, j0);
-    // C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int p = img * (OH * OW) + (i0 + 2 * wn + j) * OW + j0 + l31;
@@ -156,7 +139,7 @@ __global__ __launch_bounds__(256, P7S_OCC) void jp_igemm_p7s_kernel(const unsign
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                const int m = jp_cd_row(0, i, r, lhi);
                 if (m < M) epi.put(se, m, NS == 2 ? acc[i][j][r] * osc : acc[i][j][r]);
             }
         }

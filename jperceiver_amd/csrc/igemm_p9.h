@@ -45,20 +45,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void jp_igemm_p9_kernel(const floa
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, lhi = lane >> 5;
-    int mt, nt;
-    {   // XCD band order, see jp_igemm_kernel
-        const int gx = gridDim.x, gy = gridDim.y, G = gx & ~7;
-        const int L = blockIdx.x + blockIdx.y * gx;
-        if (L < G * gy) {
-            const int j = L >> 3;
-            mt = j % gy;
-            nt = (L & 7) * (G >> 3) + j / gy;
-        } else {
-            const int i = L - G * gy;
-            mt = i % gy;
-            nt = G + i / gy;
-        }
-    }
+    const jp_tile tile = jp_xcd_tile();
+    const int mt = tile.mt, nt = tile.nt;
     const int tiles_x = W / 32, tiles_y = H / TR;
     const int img = nt / (tiles_x * tiles_y), tr_ = nt - img * (tiles_x * tiles_y);
     const int y0 = (tr_ / tiles_x) * TR, x0 = (tr_ % tiles_x) * 32;
@@ -126,13 +114,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void jp_igemm_p9_kernel(const floa
         }
     };
 
-    jp_f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    jp_f32x16 acc[2][2] = {};
 
     // ---- weight stream of this M tile: quad Q (4 k-steps, global over stages) = 2 x BMT float4 at wt + Q*2*BMT; lane
     // (l31, lhi) reads [lhi][wm*64 + i*32 + l31] -- ONE global_load_dwordx4 per row block per 4 k-steps: a wave-uniform
@@ -198,7 +180,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void jp_igemm_p9_kernel(const floa
         __syncthreads();
     }
 
-    // C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int p = img * (int)HW + (y0 + 2 * wn + j) * W + x0 + l31;
@@ -207,7 +188,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void jp_igemm_p9_kernel(const floa
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                const int m = jp_cd_row(m0 + wm * 64, i, r, lhi);
                 if (m < M) epi.put(se, m, acc[i][j][r]);
             }
         }

@@ -106,6 +106,72 @@ __device__ __forceinline__ float jp_gather(const __amdgpu_buffer_rsrc_t& r, unsi
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, lane_bytes, uniform_bytes, 0));
 }
 
+// JP_NS == 2: the power-of-two operand scales of a split-product kernel (1 in the exact build).  Input: xsc, from its largest
+// magnitude *xam (jp_amax_of, scale.hip); weights: the pack's header {scale, 1 / scale, 0, 0}; osc undoes both on the way out
+// (exact).  wp = the pack behind its header.
+struct jp_scales { float xsc, osc; const unsigned* wp; };
+__device__ __forceinline__ jp_scales jp_operand_scales(const unsigned* __restrict__ wp, const float* __restrict__ xam) {
+    if constexpr (JP_NS == 2) {
+        const int kx = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(xam)));
+        return {jp_exp2i(kx), jp_exp2i(-kx) * __uint_as_float(__builtin_amdgcn_readfirstlane(wp[1])), wp + JP_PACK_HDR};
+    }
+    return {1.f, 1.f, wp};
+}
+// the weight-gradient form: both operands (dY: gsc from *gam, X: xsc from *xam) are tensors, no pack
+struct jp_wgrad_scales { float gsc, xsc, osc; };
+__device__ __forceinline__ jp_wgrad_scales jp_wgrad_operand_scales(const float* __restrict__ gam, const float* __restrict__ xam) {
+    if constexpr (JP_NS == 2) {
+        const int kg = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(gam))), kx = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(xam)));
+        return {jp_exp2i(kg), jp_exp2i(kx), jp_exp2i(-kg) * jp_exp2i(-kx)};
+    }
+    return {1.f, 1.f, 1.f};
+}
+
+// ---- patch staging of the stride-2 family (igemm_p9sd.h, igemm_p9s2f.h, igemm_p9s2d.h) and the weight ring they share with igemm_p7s.h.
+// A kernel builds its own staging map -- item q of a thread: soff[q] = byte offset inside the image of the first channel of k-half kh
+// (bit 0 set = zero: padding / no item), loff[q] = 16-byte LDS word inside a (split, k-half pair) plane (-1: no item) -- and these move
+// the data.
+// gather the 8 channels of every item of 16-channel stage `stage` (HW = pixels per channel)
+template <int NQ>
+__device__ __forceinline__ void jp_patch_gather(const __amdgpu_buffer_rsrc_t& xrs, const unsigned (&soff)[NQ], int stage, long HW, float (&rv)[NQ][8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int ub = __builtin_amdgcn_readfirstlane((int)(((long)stage * 16 + k) * HW * 4));     // channels past the resource read as zero
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const float v = jp_gather(xrs, soff[q] & ~1u, ub);
+            rv[q][k] = (soff[q] & 1u) ? 0.f : v;
+        }
+    }
+}
+// split every item's 8 channels and store them as one 16-byte word per split plane (SPLANE words apart) at loff[q]
+template <int SPLANE, int NQ>
+__device__ __forceinline__ void jp_patch_store(jp_u32x4* patch, const int (&loff)[NQ], const float (&rv)[NQ][8], float xsc) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        if (loff[q] < 0) continue;
+        jp_u32x4 w0, w1, w2;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            unsigned sp[3];
+            jp_split_ns(rv[q][2 * k], rv[q][2 * k + 1], xsc, sp);
+            w0[k] = sp[0]; w1[k] = sp[1]; w2[k] = sp[2];
+        }
+        patch[loff[q]] = w0;
+        patch[SPLANE + loff[q]] = w1;
+        if constexpr (JP_NS == 3) patch[2 * SPLANE + loff[q]] = w2;
+    }
+}
+// one step of the weight stream of a BMT-row M tile, [split][k-half][row] x 16 B at step_bytes of the tile's resource, into a ring slot:
+// lane offset avo = (lhi * BMT + first row of the wave + l31) * 16, the wave's two 32-row blocks are 512 bytes apart
+template <int BMT>
+__device__ __forceinline__ void jp_weight_step_load(const __amdgpu_buffer_rsrc_t& wrs, int avo, int step_bytes, jp_u32x4 (&ra)[2][JP_NS]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int s = 0; s < JP_NS; ++s) ra[i][s] = __builtin_amdgcn_raw_buffer_load_b128(wrs, avo + i * 512 + s * (2 * BMT * 16), step_bytes, 0);
+}
+
 #ifdef P9S_TRACE    // debug build only: cycle stamps of wave 0 of one workgroup (tools/debug/p1_trace.py)
 __device__ unsigned long long jp_p9s_trace[64];
 #define JP_TR(i_) do { if (TAPS == 1 && tr_on) trc_[(i_)] = __builtin_readcyclecounter(); } while (0)
@@ -169,7 +235,9 @@ __device__ __forceinline__ void jp_igemm_p9s_body(
     const float* __restrict__ xam, int s_begin = 0, int s_end = -1) {
     if (!MASK) { s_begin = 0; s_end = NST; }
     constexpr int NS = JP_NS;
-    // JP_NS == 2: operand scales.  Input: from its largest magnitude *xam (jp_amax_of, scale.hip); weights: the pack's header
+    // This body spells out the tile remap (jp_xcd_tile), the operand scales (jp_operand_scales) and the accumulator clear itself: with the
+    // helpers its kernels get the same resources but another register assignment, and one small-map instantiation then measured outside
+    // the margin (profiles/igemm_shared_helpers_ab.md).  The three blocks compute what the helpers compute; keep them in step.
     float xsc = 1.f, osc = 1.f;
     if constexpr (NS == 2) {
         const int kx = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(xam)));
@@ -210,7 +278,7 @@ __device__ __forceinline__ void jp_igemm_p9s_body(
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, lhi = lane >> 5;
     int mt, nt;
-    {   // XCD band order, see jp_igemm_kernel
+    {   // XCD band order: jp_xcd_tile()
         const int gx = gridDim.x, gy = gridDim.y, G = gx & ~7;
         const int L = blockIdx.x + blockIdx.y * gx;
         if (L < G * gy) {

@@ -16,13 +16,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void jp_igemm_p9s2d_kernel(const u
                                                                       Epi epi, int M, int C, int NST, int h2, int w2,
                                                                       const float* __restrict__ xam) {
     constexpr int NS = JP_NS;
-    float xsc = 1.f, osc = 1.f;
-    if constexpr (NS == 2) {    // operand scales, see jp_igemm_p9s_body
-        const int kx = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(xam)));
-        xsc = jp_exp2i(kx);
-        osc = jp_exp2i(-kx) * __uint_as_float(__builtin_amdgcn_readfirstlane(wp[1]));
-        wp += JP_PACK_HDR;
-    }
+    const jp_scales sc = jp_operand_scales(wp, xam);
+    const float xsc = sc.xsc, osc = sc.osc;
+    wp = sc.wp;
     constexpr int NT = 64 * WM * WN;
     constexpr int TR = WN * NJ, PR = TR + 1, COLS = 33;
     constexpr int PLANE = PR * COLS;                          // 16-byte words per (split, k-half)
@@ -35,20 +31,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void jp_igemm_p9s2d_kernel(const u
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, lhi = lane >> 5;
-    int mt, ntc;
-    {   // XCD band order, see jp_igemm_kernel
-        const int gx = gridDim.x, gy = gridDim.y, G = gx & ~7;
-        const int L = blockIdx.x + blockIdx.y * gx;
-        if (L < G * gy) {
-            const int j = L >> 3;
-            mt = j % gy;
-            ntc = (L & 7) * (G >> 3) + j / gy;
-        } else {
-            const int i = L - G * gy;
-            mt = i % gy;
-            ntc = G + i / gy;
-        }
-    }
+    const jp_tile tile = jp_xcd_tile();
+    const int mt = tile.mt, ntc = tile.nt;
     const int cls = 3 - (ntc & 3), nt = ntc >> 2;             // the 4-tap class first
     const int tiles_x = w2 / 32, tiles_y = h2 / TR;
     const int img = nt / (tiles_x * tiles_y), tr_ = nt - img * (tiles_x * tiles_y);
@@ -70,54 +54,17 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void jp_igemm_p9s2d_kernel(const u
     }
     const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xin), 0, (int)((long)C * hw2 * 4), 0x00020000);
     float rv[NQ][8];
-    auto gload = [&](int stage) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int ub = __builtin_amdgcn_readfirstlane((int)(((long)stage * 16 + k) * hw2 * 4));
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const float v = jp_gather(xrs, soff[q] & ~1u, ub);
-                rv[q][k] = (soff[q] & 1u) ? 0.f : v;
-            }
-        }
-    };
-    auto lstore = [&]() {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            if (loff[q] < 0) continue;
-            jp_u32x4 w0, w1, w2_;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                unsigned sp[3];
-                jp_split_ns(rv[q][2 * k], rv[q][2 * k + 1], xsc, sp);
-                w0[k] = sp[0]; w1[k] = sp[1]; w2_[k] = sp[2];
-            }
-            patch[loff[q]] = w0;
-            patch[2 * PLANE + loff[q]] = w1;
-            if constexpr (NS == 3) patch[4 * PLANE + loff[q]] = w2_;
-        }
-    };
+    auto gload = [&](int stage) { jp_patch_gather(xrs, soff, stage, hw2, rv); };
+    auto lstore = [&]() { jp_patch_store<2 * PLANE>(patch, loff, rv, xsc); };
 
-    jp_f32x16 acc[2][NJ];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    jp_f32x16 acc[2][NJ] = {};
 
     const long tile_bytes = ((long)NST * 9 + P9S_AHEAD) * SBYTES;
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<char*>(reinterpret_cast<const char*>(wp)) + (long)mt * tile_bytes, 0, (int)tile_bytes, 0x00020000);
     const int avo = (lhi * BMT + wm * 64 + l31) * 16;
     jp_u32x4 ra[2][2][NS];
-    auto aload = [&](int slot, int step_bytes) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-                ra[slot][i][s] = __builtin_amdgcn_raw_buffer_load_b128(wrs, avo + i * 512 + s * (2 * BMT * 16), step_bytes, 0);
-    };
+    auto aload = [&](int slot, int step_bytes) { jp_weight_step_load<BMT>(wrs, avo, step_bytes, ra[slot]); };
     const jp_u32x4* bp = patch + (lhi * PR + wn * NJ) * COLS + l31;
     jp_u32x4 rb[2][NJ][NS];
 
@@ -168,7 +115,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void jp_igemm_p9s2d_kernel(const u
             run_stage(std::integral_constant<int, 0>{}, stage);
             if (stage + 1 < NST) run_stage(std::integral_constant<int, (T & 1)>{}, stage + 1);
         }
-        // C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
         const int W = 2 * w2;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -178,7 +124,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void jp_igemm_p9s2d_kernel(const u
             for (int i = 0; i < 2; ++i) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                    const int m = jp_cd_row(m0 + wm * 64, i, r, lhi);
                     if (m < M) epi.put(se, m, NS == 2 ? acc[i][j][r] * osc : acc[i][j][r]);
                 }
             }

@@ -14,13 +14,9 @@ __global__ __launch_bounds__(256, 2) void jp_igemm_p9s2f_kernel(const unsigned* 
                                                                 Epi epi, int M, int C, int NST, int OH, int OW,
                                                                 const float* __restrict__ xam) {
     constexpr int NS = JP_NS;
-    float xsc = 1.f, osc = 1.f;
-    if constexpr (NS == 2) {    // operand scales, see jp_igemm_p9s_body
-        const int kx = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(xam)));
-        xsc = jp_exp2i(kx);
-        osc = jp_exp2i(-kx) * __uint_as_float(__builtin_amdgcn_readfirstlane(wp[1]));
-        wp += JP_PACK_HDR;
-    }
+    const jp_scales sc = jp_operand_scales(wp, xam);
+    const float xsc = sc.xsc, osc = sc.osc;
+    wp = sc.wp;
     constexpr int NT = 256, WN = 2, NJ = 2, TR = WN * NJ;
     constexpr int PR = 2 * TR + 1, COLS = 65, PODD = 34, PITS = PODD + 32;
     constexpr int PLS = PR * PITS;                           // 16-byte words per (split, k-half) plane
@@ -33,20 +29,8 @@ __global__ __launch_bounds__(256, 2) void jp_igemm_p9s2f_kernel(const unsigned* 
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, lhi = lane >> 5;
-    int mt, nt;
-    {   // XCD band order, see jp_igemm_kernel
-        const int gx = gridDim.x, gy = gridDim.y, G = gx & ~7;
-        const int L = blockIdx.x + blockIdx.y * gx;
-        if (L < G * gy) {
-            const int j = L >> 3;
-            mt = j % gy;
-            nt = (L & 7) * (G >> 3) + j / gy;
-        } else {
-            const int i = L - G * gy;
-            mt = i % gy;
-            nt = G + i / gy;
-        }
-    }
+    const jp_tile tile = jp_xcd_tile();
+    const int mt = tile.mt, nt = tile.nt;
     const int H = 2 * OH, W = 2 * OW;
     const int tiles_x = OW / 32, tiles_y = OH / TR;
     const int img = nt / (tiles_x * tiles_y), tr_ = nt - img * (tiles_x * tiles_y);
@@ -70,54 +54,17 @@ __global__ __launch_bounds__(256, 2) void jp_igemm_p9s2f_kernel(const unsigned* 
     }
     const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xin), 0, (int)((long)C * HW * 4), 0x00020000);
     float rv[NQ][8];
-    auto gload = [&](int stage) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int ub = __builtin_amdgcn_readfirstlane((int)(((long)stage * 16 + k) * HW * 4));
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const float v = jp_gather(xrs, soff[q] & ~1u, ub);
-                rv[q][k] = (soff[q] & 1u) ? 0.f : v;
-            }
-        }
-    };
-    auto lstore = [&]() {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            if (loff[q] < 0) continue;
-            jp_u32x4 w0, w1, w2_;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                unsigned sp[3];
-                jp_split_ns(rv[q][2 * k], rv[q][2 * k + 1], xsc, sp);
-                w0[k] = sp[0]; w1[k] = sp[1]; w2_[k] = sp[2];
-            }
-            patch[loff[q]] = w0;
-            patch[2 * PLS + loff[q]] = w1;
-            if constexpr (NS == 3) patch[4 * PLS + loff[q]] = w2_;
-        }
-    };
+    auto gload = [&](int stage) { jp_patch_gather(xrs, soff, stage, HW, rv); };
+    auto lstore = [&]() { jp_patch_store<2 * PLS>(patch, loff, rv, xsc); };
 
-    jp_f32x16 acc[2][NJ];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    jp_f32x16 acc[2][NJ] = {};
 
     const long tile_bytes = ((long)NST * STEPS + P9S_AHEAD) * SBYTES;
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<char*>(reinterpret_cast<const char*>(wp)) + (long)mt * tile_bytes, 0, (int)tile_bytes, 0x00020000);
     const int avo = (lhi * BMT + wm * 64 + l31) * 16;
     jp_u32x4 ra[2][2][NS];
-    auto aload = [&](int slot, int step_bytes) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-                ra[slot][i][s] = __builtin_amdgcn_raw_buffer_load_b128(wrs, avo + i * 512 + s * (2 * BMT * 16), step_bytes, 0);
-    };
+    auto aload = [&](int slot, int step_bytes) { jp_weight_step_load<BMT>(wrs, avo, step_bytes, ra[slot]); };
     aload(0, 0);
     // B fragment of tap (ky, kx), output row j of the wave: patch row 2*(wn*NJ + j) + ky, position (kx == 1 ? PODD : 0) + l31 + (kx == 2)
     const jp_u32x4* bp = patch + (lhi * PR + 2 * wn * NJ) * PITS + l31;
@@ -158,7 +105,6 @@ __global__ __launch_bounds__(256, 2) void jp_igemm_p9s2f_kernel(const unsigned* 
     }
 #undef JP_P9S2F_MFMA
 
-    // C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int p = img * (OH * OW) + (i0 + wn * NJ + j) * OW + j0 + l31;
@@ -167,7 +113,7 @@ __global__ __launch_bounds__(256, 2) void jp_igemm_p9s2f_kernel(const unsigned* 
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                const int m = jp_cd_row(m0 + wm * 64, i, r, lhi);
                 if (m < M) epi.put(se, m, NS == 2 ? acc[i][j][r] * osc : acc[i][j][r]);
             }
         }

@@ -30,20 +30,8 @@ __global__ __launch_bounds__(512, 2) void jp_igemm_p9u_kernel(const float* __res
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave >> 2, py = (wave >> 1) & 1, px = wave & 1, cls = wave & 3;
     const int l31 = lane & 31, lhi = lane >> 5;
-    int mt, nt;
-    {   // XCD band order, see jp_igemm_kernel
-        const int gx = gridDim.x, gy = gridDim.y, G = gx & ~7;
-        const int L = blockIdx.x + blockIdx.y * gx;
-        if (L < G * gy) {
-            const int j = L >> 3;
-            mt = j % gy;
-            nt = (L & 7) * (G >> 3) + j / gy;
-        } else {
-            const int i = L - G * gy;
-            mt = i % gy;
-            nt = G + i / gy;
-        }
-    }
+    const jp_tile tile = jp_xcd_tile();
+    const int mt = tile.mt, nt = tile.nt;
     const int tiles_x = W / 64, tiles_y = H / 4;
     const int img = nt / (tiles_x * tiles_y), tr_ = nt - img * (tiles_x * tiles_y);
     const int y0 = (tr_ / tiles_x) * 4, x0c = (tr_ % tiles_x) * 64;
@@ -133,13 +121,7 @@ __global__ __launch_bounds__(512, 2) void jp_igemm_p9u_kernel(const float* __res
         }
     };
 
-    jp_f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    jp_f32x16 acc[2][2] = {};
 
     // ---- B fragment bases.  S / D: pixel (row py + 2j + ty, column 2*l31 + px + tx) -> de-interleaved position
     // ((px+tx)&1)*34 + l31 + ((px+tx)>>1): taps tx = 0, 2 share a base (+0 / +1), tap tx = 1 has its own.
@@ -230,7 +212,6 @@ __global__ __launch_bounds__(512, 2) void jp_igemm_p9u_kernel(const float* __res
         stageS(std::integral_constant<int, 4>{}, offD, offD);
     }
 
-    // C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
     const int m0 = mt * 128;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -240,7 +221,7 @@ __global__ __launch_bounds__(512, 2) void jp_igemm_p9u_kernel(const float* __res
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                const int m = jp_cd_row(m0 + wm * 64, i, r, lhi);
                 if (m < M) epi.put(se, m, acc[i][j][r]);
             }
         }

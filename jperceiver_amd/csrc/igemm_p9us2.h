@@ -42,15 +42,11 @@ __global__ __launch_bounds__(512, 2) void jp_igemm_p9us2_kernel(const unsigned* 
                                                                 Epi epi, int M, int C0, int C1, int C2, int H, int W,
                                                                 const float* __restrict__ xam) {
     constexpr int NS = JP_NS;
-    // JP_NS == 2 (two fp16 splits, three products): ONE scale for the three sources -- they meet in one accumulator -- from the largest
-    // magnitude over all of them (*xam, jp_amax_of3), the weights' from the pack header of the first segment (all segments carry the same)
-    float xsc = 1.f, osc = 1.f;
-    if constexpr (NS == 2) {
-        const int kx = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(xam)));
-        xsc = jp_exp2i(kx);
-        osc = jp_exp2i(-kx) * __uint_as_float(__builtin_amdgcn_readfirstlane(wp[1]));
-        wp += JP_PACK_HDR;
-    }
+    // ONE input scale for the three sources -- they meet in one accumulator -- from the largest magnitude over all of them (*xam,
+    // jp_amax_of3); the weights' from the pack header of the first segment (all segments carry the same)
+    const jp_scales sc = jp_operand_scales(wp, xam);
+    const float xsc = sc.xsc, osc = sc.osc;
+    wp = sc.wp;
     constexpr int NT = 512, NJ = 2;
     constexpr int TR = 2 * NJ;
     constexpr int PRS = TR + 2, PHALF = 34, PITS = 2 * PHALF, COLS_S = 66; // S / D patch rows x [33 even | pad | 33 odd | pad]
@@ -67,20 +63,8 @@ __global__ __launch_bounds__(512, 2) void jp_igemm_p9us2_kernel(const unsigned* 
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave >> 2, py = (wave >> 1) & 1, px = wave & 1, cls = wave & 3;
     const int l31 = lane & 31, lhi = lane >> 5;
-    int mt, nt;
-    {   // XCD band order, see jp_igemm_kernel
-        const int gx = gridDim.x, gy = gridDim.y, G = gx & ~7;
-        const int L = blockIdx.x + blockIdx.y * gx;
-        if (L < G * gy) {
-            const int j = L >> 3;
-            mt = j % gy;
-            nt = (L & 7) * (G >> 3) + j / gy;
-        } else {
-            const int i = L - G * gy;
-            mt = i % gy;
-            nt = G + i / gy;
-        }
-    }
+    const jp_tile tile = jp_xcd_tile();
+    const int mt = tile.mt, nt = tile.nt;
 #ifdef P9S_TRACE   // debug build: per-step cycle stamps of S stage 2, waves 0, 1, 4, 5 (tools/debug/p9us_trace_steps.py)
     unsigned long long trc_[16];
     const bool tr_on = nt == 1000 && mt == 0 && lane == 0;
@@ -197,13 +181,7 @@ __global__ __launch_bounds__(512, 2) void jp_igemm_p9us2_kernel(const unsigned* 
     };
     auto lstore_stage = [&](int k, int buf) { lstore_all(k >= NS0 && k < NS0 + NS1, buf); };
 
-    jp_f32x16 acc[2][NJ];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    jp_f32x16 acc[2][NJ] = {};
 
     // ---- B fragment bases (16-byte words).  S / D: pixel (row py + 2j + ty, patch column 2*l31 + px + tx) -> de-interleaved
     // position ((px+tx)&1)*PHALF + l31 + ((px+tx)>>1): taps tx = 0, 2 share a base (+0 / +1), tap tx = 1 has its own.

@@ -22,13 +22,9 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w4s_kernel(const float* __res
                                                              int ntiles, int tiles_per_split, int dy_bytes,
                                                              const float* __restrict__ gam, const float* __restrict__ xam) {
     constexpr int NS = JP_NS;
-    float gsc = 1.f, xsc = 1.f, osc = 1.f;       // JP_NS == 2: operand scales, see jp_wgrad_w9s_kernel
-    if constexpr (NS == 2) {
-        const int kg_ = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(gam))), kx_ = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(xam)));
-        gsc = jp_exp2i(kg_);
-        xsc = jp_exp2i(kx_);
-        osc = jp_exp2i(-kg_) * jp_exp2i(-kx_);
-    }
+    // JP_NS == 2: power-of-two scales of dY and X from their largest magnitudes (scale.hip); the sums are scaled back on the way out
+    const jp_wgrad_scales sc = jp_wgrad_operand_scales(gam, xam);
+    const float gsc = sc.gsc, xsc = sc.xsc, osc = sc.osc;
     constexpr int NT = 512, PR = TR + 2, PC = 34;
     constexpr int SLOTS = PR * PC, CBP = SLOTS * 64, SPL = 2 * CBP;
     constexpr int ITEMS = SLOTS * 16, NQ = (ITEMS + NT - 1) / NT;
@@ -40,23 +36,8 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w4s_kernel(const float* __res
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int ab = wave & 3, cb = wave >> 2;
     const int l31 = lane & 31, lhi = lane >> 5;
-    int mt, nt, zs;
-    {   // every XCD owns whole K slices, see jp_wgrad_w9_kernel
-        const int gx = gridDim.x, gy = gridDim.y, T = gx * gy, SG = gridDim.z & ~7;
-        const int L3 = blockIdx.x + blockIdx.y * gx + blockIdx.z * T;
-        int tile;
-        if (L3 < SG * T) {
-            const int idx = L3 >> 3;
-            zs = (idx / T) * 8 + (L3 & 7);
-            tile = idx % T;
-        } else {
-            const int r = L3 - SG * T;
-            zs = SG + r / T;
-            tile = r % T;
-        }
-        mt = tile % gy;
-        nt = tile / gy;
-    }
+    const jp_tile tile = jp_xcd_tile_splitk();
+    const int mt = tile.mt, nt = tile.nt, zs = tile.zs;
     const int ca = zs & 1, split = zs >> 1;                   // row class a of this workgroup, K split
     const int m0 = mt * 128, c0 = nt * 64;
     const int T0 = split * tiles_per_split, T1 = min(ntiles, T0 + tiles_per_split);
@@ -133,11 +114,7 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w4s_kernel(const float* __res
         }
     };
 
-    jp_f32x16 acc[2][2][2];                                    // [b][r][s]
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j >> 2][(j >> 1) & 1][j & 1][r] = 0.f;
+    jp_f32x16 acc[2][2][2] = {};                                    // [b][r][s]
 
     if (T0 < T1) {
         int img, i0, j0;
@@ -204,7 +181,7 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w4s_kernel(const float* __res
         const long n = (long)(((ca * 2 + b) * 4) + r_ * 2 + s) * Cx + c0 + cb * 32 + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + ab * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            const int m = jp_cd_row(m0 + ab * 32, 0, r, lhi);
             if (m < Cout) wz[(long)m * Np + n] = NS == 2 ? acc[b][r_][s][r] * osc : acc[b][r_][s][r];
         }
     }

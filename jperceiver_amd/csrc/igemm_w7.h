@@ -82,11 +82,7 @@ __global__ __launch_bounds__(640) void jp_wgrad_w7_kernel(const float* __restric
         }
     };
 
-    jp_f32x16 acc[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
+    jp_f32x16 acc[2] = {};
 
     // this lane's column n = (tap, ci), tap-major; output pixel (r, c) of the tile reads input (2r + ty, 2c + tx) of the patch
     const int n = min(nb * 32 + l31, NREAL - 1);
@@ -138,7 +134,7 @@ __global__ __launch_bounds__(640) void jp_wgrad_w7_kernel(const float* __restric
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) wz[(a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi) * NP] = acc[a][r];
+        for (int r = 0; r < 16; ++r) wz[jp_cd_row(0, a, r, lhi) * NP] = acc[a][r];
 }
 
 // dw[m][ci][tap] += sum_s ws[s][m][n = tap*CIN + ci]: 64 outputs x 16 slice lanes per workgroup

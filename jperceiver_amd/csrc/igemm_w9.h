@@ -50,25 +50,8 @@ __global__ __launch_bounds__(64 * KG * MW * 3 * NB, (KG * MW * 3 * NB) / 4) void
     const int cb = wave % NB, tyw = (wave / NB) % 3, wr = (wave / (3 * NB)) % MW, kg = wave / (3 * NB * MW);
     const int l31 = lane & 31, lhi = lane >> 5;
 
-    // ---- (n tile, m tile, K slice) of this workgroup; every XCD owns whole K slices (all tiles of a slice read the same
-    // pixels of both operands: they share them through ONE L2), see jp_igemm_kernel
-    int mt, nt, zs;
-    {
-        const int gx = gridDim.x, gy = gridDim.y, T = gx * gy, SG = gridDim.z & ~7;
-        const int L3 = blockIdx.x + blockIdx.y * gx + blockIdx.z * T;
-        int tile;
-        if (L3 < SG * T) {
-            const int idx = L3 >> 3;
-            zs = (idx / T) * 8 + (L3 & 7);
-            tile = idx % T;
-        } else {
-            const int r = L3 - SG * T;
-            zs = SG + r / T;
-            tile = r % T;
-        }
-        mt = tile % gy;
-        nt = tile / gy;
-    }
+    const jp_tile tile = jp_xcd_tile_splitk();
+    const int mt = tile.mt, nt = tile.nt, zs = tile.zs;
     const int m0 = mt * 64 * MW, c0 = nt * NC;
     const int T0 = zs * tiles_per_split, T1 = min(ntiles, T0 + tiles_per_split);
     const int tiles_x = W / 32, tiles_img = tiles_x * (H / TR);
@@ -144,13 +127,7 @@ __global__ __launch_bounds__(64 * KG * MW * 3 * NB, (KG * MW * 3 * NB) / 4) void
         }
     };
 
-    jp_f32x16 acc[2][3];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][j][r] = 0.f;
+    jp_f32x16 acc[2][3] = {};
 
     // B fragment of k-step (tr, q, j), tap (tyw, tx): pixel (tr + tyw, 8q + 4*lhi + j + tx) of the patch
     const float* bp = patch + (((tyw + kg * TRG) * PC) + 4 * lhi) * LDB + cb * 32 + l31;
@@ -212,7 +189,7 @@ __global__ __launch_bounds__(64 * KG * MW * 3 * NB, (KG * MW * 3 * NB) / 4) void
         for (int a = 0; a < 2; ++a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                const int m = jp_cd_row(m0 + wr * 64, a, r, lhi);
                 if (m < Cout) wz[(long)m * Np + n] = acc[a][j][r];
             }
         }
@@ -237,23 +214,8 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w1_kernel(const float* __rest
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wr = wave >> 1, cbw = wave & 1;
     const int l31 = lane & 31, lhi = lane >> 5;
-    int mt, nt, zs;
-    {   // every XCD owns whole K slices, see jp_wgrad_w9_kernel
-        const int gx = gridDim.x, gy = gridDim.y, T = gx * gy, SG = gridDim.z & ~7;
-        const int L3 = blockIdx.x + blockIdx.y * gx + blockIdx.z * T;
-        int tile;
-        if (L3 < SG * T) {
-            const int idx = L3 >> 3;
-            zs = (idx / T) * 8 + (L3 & 7);
-            tile = idx % T;
-        } else {
-            const int r = L3 - SG * T;
-            zs = SG + r / T;
-            tile = r % T;
-        }
-        mt = tile % gy;
-        nt = tile / gy;
-    }
+    const jp_tile tile = jp_xcd_tile_splitk();
+    const int mt = tile.mt, nt = tile.nt, zs = tile.zs;
     const int m0 = mt * 256, c0 = nt * NC;
     const int T0 = zs * tiles_per_split, T1 = min(ntiles, T0 + tiles_per_split);
     const int tiles_x = W / 32, tiles_img = tiles_x * (H / TR);
@@ -296,13 +258,7 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w1_kernel(const float* __rest
 #pragma unroll
         for (int r = 0; r < NROWS; ++r) pd[4 * r] = rb[r];
     };
-    jp_f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][j][r] = 0.f;
+    jp_f32x16 acc[2][2] = {};
     const float* bp = patch + (4 * lhi) * LDB + cbw * 64 + l31;
     if (T0 < T1) {
         int img, y0, x0;
@@ -352,7 +308,7 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w1_kernel(const float* __rest
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                const int m = jp_cd_row(m0 + wr * 64, a, r, lhi);
                 if (m < Cout) wz[(long)m * Cm + n] = acc[a][j][r];
             }
     }

@@ -44,13 +44,8 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w9s_kernel(const float* __res
                                                              const float* __restrict__ gam, const float* __restrict__ xam) {
     constexpr int NS = JP_NS;
     // JP_NS == 2: power-of-two scales of dY and X from their largest magnitudes (scale.hip); the sums are scaled back on the way out
-    float gsc = 1.f, xsc = 1.f, osc = 1.f;
-    if constexpr (NS == 2) {
-        const int kg_ = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(gam))), kx_ = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(xam)));
-        gsc = jp_exp2i(kg_);
-        xsc = jp_exp2i(kx_);
-        osc = jp_exp2i(-kg_) * jp_exp2i(-kx_);
-    }
+    const jp_wgrad_scales sc = jp_wgrad_operand_scales(gam, xam);
+    const float gsc = sc.gsc, xsc = sc.xsc, osc = sc.osc;
     constexpr int NT = 512, PR = TR + 2, PC = 34;
     constexpr int SLOTS = PR * PC;                 // patch pixels
     constexpr int CBP = SLOTS * 64;                // bytes per (split, channel block) plane
@@ -70,23 +65,8 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w9s_kernel(const float* __res
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int ab = wave % MB, cb = (wave / MB) % NCB, kg = wave / (NCB * MB);
     const int l31 = lane & 31, lhi = lane >> 5;
-    int mt, nt, zs;
-    {   // every XCD owns whole K slices, see jp_wgrad_w9_kernel
-        const int gx = gridDim.x, gy = gridDim.y, T = gx * gy, SG = gridDim.z & ~7;
-        const int L3 = blockIdx.x + blockIdx.y * gx + blockIdx.z * T;
-        int tile;
-        if (L3 < SG * T) {
-            const int idx = L3 >> 3;
-            zs = (idx / T) * 8 + (L3 & 7);
-            tile = idx % T;
-        } else {
-            const int r = L3 - SG * T;
-            zs = SG + r / T;
-            tile = r % T;
-        }
-        mt = tile % gy;
-        nt = tile / gy;
-    }
+    const jp_tile tile = jp_xcd_tile_splitk();
+    const int mt = tile.mt, nt = tile.nt, zs = tile.zs;
     const int m0 = mt * 32 * MB, c0 = nt * 32 * NCB;
     const int T0 = zs * tiles_per_split, T1 = min(ntiles, T0 + tiles_per_split);
     const int tiles_x = W / 32, tiles_img = tiles_x * (H / TR);
@@ -172,11 +152,7 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w9s_kernel(const float* __res
         for (int q = 0; q < NQ; ++q) lstore1(q, wbuf);
     };
 
-    jp_f32x16 acc[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    jp_f32x16 acc[9] = {};
 
     // Round 5: the instruction stream is laid out for an in-order wave that shares its SIMD's matrix pipe with ONE partner which the
     // arbiter serves strictly by age (tools/ubench/mfma_lone_wave.hip: of two waves with MFMAs ready the older issues all of its
@@ -317,7 +293,7 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w9s_kernel(const float* __res
         const long n = (long)tap * Cm + c0 + cb * 32 + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + ab * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            const int m = jp_cd_row(m0 + ab * 32, 0, r, lhi);
             if (m < Cout) wz[(long)m * Np + n] = NS == 2 ? acc[tap][r] * osc : acc[tap][r];
         }
     }
@@ -338,13 +314,9 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w1s_kernel(const float* __res
                                                              int ntiles, int tiles_per_split, int dy_bytes,
                                                              const float* __restrict__ gam, const float* __restrict__ xam) {
     constexpr int NS = JP_NS;
-    float gsc = 1.f, xsc = 1.f, osc = 1.f;       // JP_NS == 2: operand scales, see jp_wgrad_w9s_kernel
-    if constexpr (NS == 2) {
-        const int kg_ = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(gam))), kx_ = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(xam)));
-        gsc = jp_exp2i(kg_);
-        xsc = jp_exp2i(kx_);
-        osc = jp_exp2i(-kg_) * jp_exp2i(-kx_);
-    }
+    // JP_NS == 2: power-of-two scales of dY and X from their largest magnitudes (scale.hip); the sums are scaled back on the way out
+    const jp_wgrad_scales sc = jp_wgrad_operand_scales(gam, xam);
+    const float gsc = sc.gsc, xsc = sc.xsc, osc = sc.osc;
     constexpr int NT = 512, TR = 4, NC = 128, P = TR * 32;
     constexpr int PITCH = P * 2 + 16;                 // bytes per channel row of one split plane
     constexpr int SPL = NC * PITCH;                   // bytes per split plane
@@ -354,23 +326,8 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w1s_kernel(const float* __res
     const int t = threadIdx.x, lane = t & 63;
     const int ab = __builtin_amdgcn_readfirstlane(t >> 6);
     const int l31 = lane & 31, lhi = lane >> 5;
-    int mt, nt, zs;
-    {   // every XCD owns whole K slices, see jp_wgrad_w9_kernel
-        const int gx = gridDim.x, gy = gridDim.y, T = gx * gy, SG = gridDim.z & ~7;
-        const int L3 = blockIdx.x + blockIdx.y * gx + blockIdx.z * T;
-        int tile;
-        if (L3 < SG * T) {
-            const int idx = L3 >> 3;
-            zs = (idx / T) * 8 + (L3 & 7);
-            tile = idx % T;
-        } else {
-            const int r = L3 - SG * T;
-            zs = SG + r / T;
-            tile = r % T;
-        }
-        mt = tile % gy;
-        nt = tile / gy;
-    }
+    const jp_tile tile = jp_xcd_tile_splitk();
+    const int mt = tile.mt, nt = tile.nt, zs = tile.zs;
     const int m0 = mt * 256, c0 = nt * NC;
     const int T0 = zs * tiles_per_split, T1 = min(ntiles, T0 + tiles_per_split);
     const int tiles_x = W / 32, tiles_img = tiles_x * (H / TR);
@@ -424,11 +381,7 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w1s_kernel(const float* __res
             if constexpr (NS == 3) *reinterpret_cast<jp_u32x4*>(d + 2 * SPL) = w2;
         }
     };
-    jp_f32x16 acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    jp_f32x16 acc[4] = {};
     // B fragment of K group g (tile row g/2, columns 16*(g%2) + 8*lhi .. +7 = octet 4*(g/2) + 2*(g%2) + lhi), block j, split s
     const unsigned char* bp = patch + l31 * PITCH + lhi * 16;
     auto bread = [&](int g, int j, int s) -> jp_u32x4 {
@@ -488,7 +441,7 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w1s_kernel(const float* __res
         const long n = c0 + j * 32 + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + ab * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            const int m = jp_cd_row(m0 + ab * 32, 0, r, lhi);
             if (m < Cout) wz[(long)m * Cm + n] = NS == 2 ? acc[j][r] * osc : acc[j][r];
         }
     }

@@ -25,13 +25,9 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w9s2_kernel(const float* __re
                                                               int ntiles, int tiles_per_split, int dy_bytes, int x_bytes,
                                                               const float* __restrict__ gam, const float* __restrict__ xam) {
     constexpr int NS = JP_NS;
-    float gsc = 1.f, xsc = 1.f, osc = 1.f;       // JP_NS == 2: operand scales, see jp_wgrad_w9s_kernel
-    if constexpr (NS == 2) {
-        const int kg_ = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(gam))), kx_ = __builtin_amdgcn_readfirstlane(jp_scale_exp(jp_slot_amax(xam)));
-        gsc = jp_exp2i(kg_);
-        xsc = jp_exp2i(kx_);
-        osc = jp_exp2i(-kg_) * jp_exp2i(-kx_);
-    }
+    // JP_NS == 2: power-of-two scales of dY and X from their largest magnitudes (scale.hip); the sums are scaled back on the way out
+    const jp_wgrad_scales sc = jp_wgrad_operand_scales(gam, xam);
+    const float gsc = sc.gsc, xsc = sc.xsc, osc = sc.osc;
     constexpr int NT = 512, TR = 2;
     constexpr int PRX = 2 * TR + 1, PCX = 65;      // patch rows / columns in input pixels
     constexpr int PRP = TR + 1, PCP = 34;          // rows / row pitch of one parity plane
@@ -48,23 +44,8 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w9s2_kernel(const float* __re
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int ab = wave % MB, kg = wave / MB;
     const int l31 = lane & 31, lhi = lane >> 5;
-    int mt, nt, zs;
-    {   // every XCD owns whole K slices, see jp_wgrad_w9_kernel
-        const int gx = gridDim.x, gy = gridDim.y, T = gx * gy, SG = gridDim.z & ~7;
-        const int L3 = blockIdx.x + blockIdx.y * gx + blockIdx.z * T;
-        int tile;
-        if (L3 < SG * T) {
-            const int idx = L3 >> 3;
-            zs = (idx / T) * 8 + (L3 & 7);
-            tile = idx % T;
-        } else {
-            const int r = L3 - SG * T;
-            zs = SG + r / T;
-            tile = r % T;
-        }
-        mt = tile % gy;
-        nt = tile / gy;
-    }
+    const jp_tile tile = jp_xcd_tile_splitk();
+    const int mt = tile.mt, nt = tile.nt, zs = tile.zs;
     const int m0 = mt * 32 * MB, c0 = nt * 32;
     const int T0 = zs * tiles_per_split, T1 = min(ntiles, T0 + tiles_per_split);
     const int tiles_x = OW / 32, tiles_img = tiles_x * (OH / TR);
@@ -155,11 +136,7 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w9s2_kernel(const float* __re
         }
     };
 
-    jp_f32x16 acc[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    jp_f32x16 acc[9] = {};
 
     if (T0 < T1) {
         int img, y0, x0;
@@ -219,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void jp_wgrad_w9s2_kernel(const float* __re
         const long n = (long)tap * Cm + c0 + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + ab * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            const int m = jp_cd_row(m0 + ab * 32, 0, r, lhi);
             if (m < Cout) wz[(long)m * Np + n] = NS == 2 ? acc[tap][r] * osc : acc[tap][r];
         }
     }

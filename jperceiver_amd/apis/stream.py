@@ -23,7 +23,12 @@ THE RETURNED TENSORS ARE THE SESSION'S STATIC OUTPUT BUFFERS: they are valid unt
 overwrites them in place -- clone what has to live longer.
 
 Frames in pinned host memory are copied without blocking: the caller must leave that buffer untouched until the copy has run
-(an event recorded after `push`, or any later synchronisation, tells)."""
+(an event recorded after `push`, or any later synchronisation, tells).
+
+bev_map=True (or a dict of BevMap keyword arguments): every push ends with one more launch, jp_bev_fuse, which votes the frame's
+layout into a world-frame map with the pose jp_stream_traj_push has just finished (apis/bevmap.py).  `s.bev_map` is the live `BevMap`
+-- it accumulates, it is not a per-frame static buffer -- and exists after the first push, which tells the layouts' size.  The
+default (None) adds nothing to a push."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -49,9 +54,13 @@ class StreamFrame(NamedTuple):
 class PerceptionStream:
     """See the module docstring.  model: an eval-mode `Baseline` on the GPU that holds a checkpoint; src_hw: (h, w) of the camera
     frames; out_size: (OH, OW) of the depth maps (default: the network's resolution); min_depth / max_depth default to
-    model.opt's; capacity: trajectory rows kept per camera (later frames still update `pose`)."""
+    model.opt's; capacity: trajectory rows kept per camera (later frames still update `pose`); bev_map: None, True or a dict of
+    `BevMap` keyword arguments (`off` defaults from model.opt.split, `occ` is the layouts')."""
 
-    def __init__(self, model, src_hw, cameras=1, out_size=None, min_depth=None, max_depth=None, capacity=4096, frozen=True):
+    def __init__(self, model, src_hw, cameras=1, out_size=None, min_depth=None, max_depth=None, capacity=4096, frozen=True,
+                 bev_map=None):
+        if not (bev_map is None or bev_map is True or isinstance(bev_map, dict)):
+            raise TypeError("bev_map must be None, True or a dict of BevMap keyword arguments")
         if model.training:
             raise RuntimeError("PerceptionStream expects an eval-mode model (call .eval(): BatchNorm must use running stats)")
         p = next(model.parameters())
@@ -82,12 +91,18 @@ class PerceptionStream:
         self._depth = torch.empty((B, 1) + self.out_size, device=dev)
         self._disp = self._layout = None                              # shaped by the first pass
         self._n = 0
+        self._bev_kw = None if bev_map is None else dict(bev_map if isinstance(bev_map, dict) else {})
+        if self._bev_kw is not None:
+            self._bev_kw.setdefault("off", 1.9 if getattr(model.opt, "split", None) == "argo" else 0.27)
+        self.bev_map = None                                           # the live BevMap: made by the first push of a bev_map session
 
     # ---------------------------------------------------------------------------------------- state
     def reset(self):
         """Forget the stream: the next frame is frame 0 again (paired with itself, pose = I, trajectory row 0)."""
         for t in (self._count, self._ring, self._pose, self._traj, self._T):
             t.zero_()
+        if self.bev_map is not None:
+            self.bev_map.reset()
         self._n = 0
 
     def trajectory(self):
@@ -131,6 +146,13 @@ class PerceptionStream:
         aa, tr = m.eval_branch("pose", Var(pair))
         ops.call("jp_pose_fwd", aa.t, tr.t, self._K, self._T, self._P, B, 1)
         ops.call("jp_stream_traj_push", self._T, self._pose, self._traj, self._count, B, self.capacity)
+        if self._bev_kw is not None:
+            if self.bev_map is None:
+                if h != w:
+                    raise ValueError(f"bev_map needs square layouts, the model's are {h} x {w}")
+                from .bevmap import BevMap
+                self.bev_map = BevMap(B, h, **{**self._bev_kw, "device": dev})
+            self.bev_map._fuse(self._layout, self._pose, 16, 1)       # behind traj_push: the pose it reads is finished
 
     @torch.no_grad()
     def push(self, frames_u8) -> StreamFrame:

@@ -168,6 +168,39 @@ GROUPS = [
      "after every camera is done: jp_stream_pose_pair of a frame must be enqueued BEFORE its jp_stream_traj_push (one stream, or an "
      "event in between).  One workgroup, no atomics.",
      ["jp_stream_pose_pair", "jp_stream_traj_push"]),
+    ("World-frame BEV map (csrc/bevmap.hip; apis/bevmap.py BevMap, PerceptionStream(bev_map=...)) -- the ego-centred class maps of a drive "
+     "voted into ONE map with the drive's float64 poses; no counterpart in the reference (scripts/eval_kitti_video.py shows the current "
+     "layout beside a plotted trajectory).  The map, the image and the poses are the caller's buffers (the library keeps no state).  "
+     "GEOMETRY: world is the frame of camera pose T_0 = I; +X goes to increasing map columns, +Z (forward) to decreasing rows, world (0, 0) "
+     "sits at cell coordinates (org_r, org_c), cells are res metres a side.  Frame cell (i, j) covers x in [(j - occ/2) res_f, "
+     "(j + 1 - occ/2) res_f) and z in [(occ - 1 - i) res_f - off, (occ - i) res_f - off): row i's far edge is the forward distance of "
+     + R + "net.py:230-242 (_distance_map); res_f = 40 / occ, off = 0.27 (KITTI) or 1.9 (split == 'argo').  THE BEV PLANE IS TAKEN TO "
+     "BE THE CAMERA'S OWN x-z PLANE: the shift h R[.][1] from the camera's height above the ground is dropped.  "
+     "jp_bev_fuse: layout (B,N,occ,occ) bytes with the classes of jp_layout_classes_u8 (0 background, 1 road, 2 car); pose: for camera b, "
+     "frame n the row-major 3x4 or 4x4 camera-to-world transform at pose + (b N + n) pose_stride doubles (pose_stride 16: the session's "
+     "pose; 12: trajectory rows; >= 12), of which only T[0][0], T[0][2], T[0][3], T[2][0], T[2][2], T[2][3] are read; counts (B,3,Mh,Mw) "
+     "int32 [seen, road, car], read-modify-write: it accumulates over calls.  A GATHER: for map cell (r, c) and every frame, in float64 "
+     "with every operation rounded once (no fma) and in exactly this order: X = ((c + 0.5) - org_c) res, Z = ((org_r - r) - 0.5) res, "
+     "dX = X - T[0][3], dZ = Z - T[2][3], det = T[0][0] T[2][2] - T[0][2] T[2][0], x = (T[2][2] dX - T[0][2] dZ) / det, "
+     "z = (T[0][0] dZ - T[2][0] dX) / det, u = x / res_f + occ / 2 (occ / 2 in float64: 0.5 occ), v = (z + off) / res_f; a hit iff "
+     "u >= 0 && u < occ && v >= 0 && v < occ && z <= max_range, then j = floor(u), i = occ - 1 - floor(v), cls = layout[b][n][i][j]: "
+     "seen += 1, road += (cls == 1), car += (cls == 2).  A frame with !(|det| >= 1e-6) contributes nothing (that covers a NaN det); every "
+     "range test is false for NaN and nothing is converted to an integer before its test has passed.  The kernel does not sweep the map: per "
+     "frame it visits a square window of ceil(occ res_f sqrt(2) / res) + 3 cells a side (at most 32768) whose map origin it computes ITSELF "
+     "from the pose, around the footprint centre T (0, 0, occ res_f / 2 - off) (= 20 - off) -- the launch arguments of a session's push are the "
+     "same for every frame; cells of the window outside the map are skipped, and so is a frame whose window misses the map or whose "
+     "centre is not finite.  The window covers the footprint of every pose whose x-z block has singular values <= 1 (any rigid transform).  "
+     "N == 1: one thread owns each map cell, no atomics; N > 1: the frames run in parallel with integer atomicAdd -- integer sums do not "
+     "depend on the order, two runs give the same counts.  B N <= 65535.  ORDERING: enqueue a frame's jp_bev_fuse AFTER its "
+     "jp_stream_traj_push on the same stream (the pose it reads is finished by that launch).  "
+     "jp_bev_map_classes: counts (B,3,cells) -> cls (B,cells) bytes and (nullable) rgb (B,cells,3); counts are converted to double (exact) "
+     "and the rules apply in this order: seen < min_seen -> 255; car >= car_frac seen -> 2; road + car >= road_frac seen -> 1 (a car "
+     "stands on road); else 0.  Palette of jp_layout_classes_u8, and (96,96,96) for 255.  "
+     "jp_bev_map_mark: traj (B,capacity,12) doubles; for each of the first n (<= capacity) rows of every camera the cell "
+     "(floor(org_r - T[2][3] / res), floor(T[0][3] / res + org_c)) of rgb (B,Mh,Mw,3) is painted with color = R | G << 8 | B << 16; rows "
+     "that fall outside the map or are not finite are skipped; several rows may write the same bytes to one cell.  "
+     "All three refuse null pointers, non-positive sizes and res / res_f that are not greater than zero before any launch.",
+     ["jp_bev_fuse", "jp_bev_map_classes", "jp_bev_map_mark"]),
     ("KITTI odometry evaluation (csrc/odometry.hip; core/evaluation.py::eval_odometry, apis/inference.py) — the pose chaining of "
      "scripts/draw_odometry.py:62-76 and the numpy toolkit behind the paper's t_err / r_err (mono/tools/kitti_evaluation_toolkit.py:"
      "109-201, mono/tools/geometry.py:20-67, scripts/plot_kitti.py:15-97,223-243).  All arithmetic is double, no atomics: every sum "

@@ -28,7 +28,14 @@ Frames in pinned host memory are copied without blocking: the caller must leave 
 bev_map=True (or a dict of BevMap keyword arguments): every push ends with one more launch, jp_bev_fuse, which votes the frame's
 layout into a world-frame map with the pose jp_stream_traj_push has just finished (apis/bevmap.py).  `s.bev_map` is the live `BevMap`
 -- it accumulates, it is not a per-frame static buffer -- and exists after the first push, which tells the layouts' size.  The
-default (None) adds nothing to a push."""
+default (None) adds nothing to a push.
+
+depth_bev=dict(K=..., ...) (keyword arguments of `DepthBev`, apis/depthbev.py; K, the pixel intrinsics of the camera frames, is
+required): every push enqueues three more launches with the same arguments for every frame -- jp_depth_bev_lift (its fill
+included) behind jp_disp_resize_depth, jp_depth_bev_classes behind jp_layout_classes_u8 and jp_bev_agree after that.
+`s.depth_bev` is the live `DepthBev`; its `.grid`, `.cls` and `.agree` are static buffers with the lifetime of the other
+outputs.  `off` defaults from model.opt.split, `occ` is model.opt.occ_map_size, the depth maps are `out_size`.  The default
+(None) adds nothing to a push."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -55,12 +62,18 @@ class PerceptionStream:
     """See the module docstring.  model: an eval-mode `Baseline` on the GPU that holds a checkpoint; src_hw: (h, w) of the camera
     frames; out_size: (OH, OW) of the depth maps (default: the network's resolution); min_depth / max_depth default to
     model.opt's; capacity: trajectory rows kept per camera (later frames still update `pose`); bev_map: None, True or a dict of
-    `BevMap` keyword arguments (`off` defaults from model.opt.split, `occ` is the layouts')."""
+    `BevMap` keyword arguments (`off` defaults from model.opt.split, `occ` is the layouts'); depth_bev: None or a dict of
+    `DepthBev` keyword arguments with at least K (`off` defaults from model.opt.split; cameras, occ, src_hw, depth_hw and device
+    are the session's)."""
 
     def __init__(self, model, src_hw, cameras=1, out_size=None, min_depth=None, max_depth=None, capacity=4096, frozen=True,
-                 bev_map=None):
+                 bev_map=None, depth_bev=None):
         if not (bev_map is None or bev_map is True or isinstance(bev_map, dict)):
             raise TypeError("bev_map must be None, True or a dict of BevMap keyword arguments")
+        if not (depth_bev is None or isinstance(depth_bev, dict)):
+            raise TypeError("depth_bev must be None or a dict of DepthBev keyword arguments (K is required)")
+        if depth_bev is not None and "K" not in depth_bev:
+            raise ValueError("depth_bev needs K, the pixel intrinsics of the camera frames")
         if model.training:
             raise RuntimeError("PerceptionStream expects an eval-mode model (call .eval(): BatchNorm must use running stats)")
         p = next(model.parameters())
@@ -95,6 +108,12 @@ class PerceptionStream:
         if self._bev_kw is not None:
             self._bev_kw.setdefault("off", 1.9 if getattr(model.opt, "split", None) == "argo" else 0.27)
         self.bev_map = None                                           # the live BevMap: made by the first push of a bev_map session
+        self.depth_bev = None                                         # the live DepthBev of a depth_bev session
+        if depth_bev is not None:
+            from .depthbev import DepthBev
+            kw = {"off": 1.9 if getattr(model.opt, "split", None) == "argo" else 0.27, **depth_bev}
+            kw.update(cameras=B, occ=int(model.opt.occ_map_size), src_hw=self.src_hw, depth_hw=self.out_size, device=dev)
+            self.depth_bev = DepthBev(**kw)
 
     # ---------------------------------------------------------------------------------------- state
     def reset(self):
@@ -103,6 +122,8 @@ class PerceptionStream:
             t.zero_()
         if self.bev_map is not None:
             self.bev_map.reset()
+        if self.depth_bev is not None:
+            self.depth_bev.reset()
         self._n = 0
 
     def trajectory(self):
@@ -134,11 +155,19 @@ class PerceptionStream:
         ops.call("jp_axpby", disp, None, self._disp, disp.numel(), 1.0, 0.0)
         ops.call("jp_disp_resize_depth", self._disp, self._depth, None, B, h, w, self.out_size[0], self.out_size[1],
                  self.min_depth, self.max_depth)
+        db = self.depth_bev
+        if db is not None:
+            db._lift(self._depth, False)
         road, car = m.eval_branch("layout_heads", m.eval_branch("layout_encoder", x), feats[-1])
         h, w = road.shape[2:]
         if self._layout is None:
             self._layout = torch.empty((B, h, w), device=dev, dtype=torch.uint8)
         ops.call("jp_layout_classes_u8", road, car, self._layout, None, B, h * w)
+        if db is not None:
+            if (h, w) != (db.occ, db.occ):
+                raise ValueError(f"depth_bev: the layouts are {h} x {w}, model.opt.occ_map_size says {db.occ}")
+            db._classes(False)
+            db._agree(self._layout)
         pair = torch.empty((B, 6, _PH, _PW), device=dev)
         # (no magnitude slot: the pose encoder normalises the pair into a new tensor first (ops.affine), and the stem convolution
         # reduces the magnitude of THAT input itself where its kernel reads one -- nothing reads max |pair|)

@@ -201,6 +201,37 @@ GROUPS = [
      "that fall outside the map or are not finite are skipped; several rows may write the same bytes to one cell.  "
      "All three refuse null pointers, non-positive sizes and res / res_f that are not greater than zero before any launch.",
      ["jp_bev_fuse", "jp_bev_map_classes", "jp_bev_map_mark"]),
+    ("Depth lifted into the layout's BEV grid and depth-layout agreement (csrc/depthbev.hip; apis/depthbev.py DepthBev, "
+     "PerceptionStream(depth_bev=...)) -- the inverse of the training-time warp of " + R + "net.py:193-267 (get_scale_label_static takes "
+     "the BEV distance map into the image; jp_scale_label_assemble here): every depth pixel is placed in the frame-cell geometry of "
+     "jp_bev_fuse above (cell (i, j) covers x in [(j - occ/2) res_f, (j + 1 - occ/2) res_f) and z in [(occ - 1 - i) res_f - off, "
+     "(occ - i) res_f - off); res_f = 40 / occ, off = 0.27 (KITTI) or 1.9 (split == 'argo')).  No counterpart at inference in the "
+     "reference.  Every buffer is the caller's (the library keeps no state).  "
+     "jp_depth_bev_lift: depth (B,1,H,W) float metres; cam (B,8) doubles in device memory [fx, fy, cx, cy, nx, ny, nz, h]: pixel intrinsics "
+     "at the resolution of depth, and the ground plane in the camera frame (height above ground of a camera-frame point P is h - n.P; "
+     "(0, 1, 0, camera height) for a level camera whose y axis points down); grid (B,4,occ,occ) int32 planes [n, n_obst, hmin_mm, "
+     "hmax_mm].  accumulate == 0: the call first fills grid with [0, 0, INT_MAX, INT_MIN] by a launch of its own on the same stream, the "
+     "result is a pure function of the inputs; accumulate != 0: it adds to what grid holds.  Per pixel (u, v) -- integer pixel "
+     "coordinates, as Backproject's meshgrid (" + R + "layers.py:41-63) -- in float64 with every operation rounded once (no fma) and in "
+     "exactly this order: (1) d = (double)depth; accept iff d >= min_range && d <= max_range (false for NaN and +Inf).  "
+     "(2) X = ((u - cx) / fx) d.  (3) Y = ((v - cy) / fy) d.  (4) hgt = h - ((nx X + ny Y) + nz d); accept iff hgt >= h_min && "
+     "hgt <= h_max.  (5) uu = X / res_f + 0.5 occ (0.5 occ exact in float64), vv = (d + off) / res_f; accept iff 0 <= uu < occ && "
+     "0 <= vv < occ.  (6) j = floor(uu), i = occ - 1 - floor(vv).  (7) q = (int)floor(hgt 1000 + 0.5).  Nothing is converted to an "
+     "integer before its test has passed.  An accepted pixel updates cell (i, j) of its camera: n += 1, n_obst += (hgt > obst_h), "
+     "hmin_mm = min(hmin_mm, q), hmax_mm = max(hmax_mm, q), with integer atomicAdd / atomicMin / atomicMax: order-free, two runs give "
+     "the same bits.  Two forms of the kernel give the same grid: per-lane atomics, or (default; JP_DEPTH_BEV_RUNS=0 selects the "
+     "other, read at every call) a wave folds each run of consecutive lanes with the same cell by a segmented scan and the run's last "
+     "lane issues the atomics (profiles/depth_bev.md).  Refused before any launch: null pointers, non-positive sizes, res_f <= 0, "
+     "|h_min| or |h_max| > 1e6 (heights are int32 millimetres), B H W >= 2^31, B 4 occ occ >= 2^31.  "
+     "jp_depth_bev_classes: grid (B,4,cells) -> cls (B,cells) bytes, rules in this order: n < min_points -> 255 (not observed); "
+     "n_obst >= obst_points -> 2 (obstacle); else 1 (ground); height (B,cells) float, nullable: (float)hmax_mm / 1000.0f (float "
+     "division, rounded once), NaN where cls is 255.  "
+     "jp_bev_agree: lifted, layout (B,cells) bytes -> out (B,2,3) int32, OVERWRITTEN: out[b][l-1][c] = cells with lifted == l (1 ground, "
+     "2 obstacle) and layout == c (0 background, 1 road, 2 car, the classes of jp_layout_classes_u8); cells whose lifted class is 255 "
+     "(or anything but 1 / 2) or whose layout value is above 2 count nowhere.  One workgroup per camera, integer sums, no atomics, no "
+     "workgroup waits on another.  ORDERING in a session: the lift behind jp_disp_resize_depth, the classes behind the lift, "
+     "jp_bev_agree behind both jp_depth_bev_classes and jp_layout_classes_u8, all on one stream.",
+     ["jp_depth_bev_lift", "jp_depth_bev_classes", "jp_bev_agree"]),
     ("KITTI odometry evaluation (csrc/odometry.hip; core/evaluation.py::eval_odometry, apis/inference.py) — the pose chaining of "
      "scripts/draw_odometry.py:62-76 and the numpy toolkit behind the paper's t_err / r_err (mono/tools/kitti_evaluation_toolkit.py:"
      "109-201, mono/tools/geometry.py:20-67, scripts/plot_kitti.py:15-97,223-243).  All arithmetic is double, no atomics: every sum "

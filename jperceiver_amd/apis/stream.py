@@ -35,7 +35,13 @@ required): every push enqueues three more launches with the same arguments for e
 included) behind jp_disp_resize_depth, jp_depth_bev_classes behind jp_layout_classes_u8 and jp_bev_agree after that.
 `s.depth_bev` is the live `DepthBev`; its `.grid`, `.cls` and `.agree` are static buffers with the lifetime of the other
 outputs.  `off` defaults from model.opt.split, `occ` is model.opt.occ_map_size, the depth maps are `out_size`.  The default
-(None) adds nothing to a push."""
+(None) adds nothing to a push.
+
+depth_bev=dict(K=..., ground=True) (or ground=dict(...), the `ground` argument of `DepthBev`): the ground plane is fitted from
+every frame's depth (and, with use_layout, the road cells of its layout) before the lift measures heights against it.  The order
+of a push becomes jp_layout_classes_u8 -> jp_ground_fit -> jp_depth_bev_lift -> jp_depth_bev_classes -> jp_bev_agree: the lift
+moves behind the layout, in this kind of session only, and every launch still has fixed arguments (the plane travels in device
+memory).  `s.depth_bev.ground()` reads the live plane, its status and the height ratio (the one synchronising step)."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -74,6 +80,9 @@ class PerceptionStream:
             raise TypeError("depth_bev must be None or a dict of DepthBev keyword arguments (K is required)")
         if depth_bev is not None and "K" not in depth_bev:
             raise ValueError("depth_bev needs K, the pixel intrinsics of the camera frames")
+        if depth_bev is not None and depth_bev.get("ground") is not None:
+            from .depthbev import _ground_kw
+            _ground_kw(depth_bev["ground"])                           # a malformed `ground` is refused before anything else is looked at
         if model.training:
             raise RuntimeError("PerceptionStream expects an eval-mode model (call .eval(): BatchNorm must use running stats)")
         p = next(model.parameters())
@@ -156,7 +165,8 @@ class PerceptionStream:
         ops.call("jp_disp_resize_depth", self._disp, self._depth, None, B, h, w, self.out_size[0], self.out_size[1],
                  self.min_depth, self.max_depth)
         db = self.depth_bev
-        if db is not None:
+        fit = db is not None and db.ground_kw is not None              # a ground session: the lift waits for the fit, the fit for the layout
+        if db is not None and not fit:
             db._lift(self._depth, False)
         road, car = m.eval_branch("layout_heads", m.eval_branch("layout_encoder", x), feats[-1])
         h, w = road.shape[2:]
@@ -166,6 +176,9 @@ class PerceptionStream:
         if db is not None:
             if (h, w) != (db.occ, db.occ):
                 raise ValueError(f"depth_bev: the layouts are {h} x {w}, model.opt.occ_map_size says {db.occ}")
+            if fit:
+                db._fit(self._depth, self._layout)
+                db._lift(self._depth, False)
             db._classes(False)
             db._agree(self._layout)
         pair = torch.empty((B, 6, _PH, _PW), device=dev)

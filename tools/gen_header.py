@@ -232,6 +232,42 @@ GROUPS = [
      "workgroup waits on another.  ORDERING in a session: the lift behind jp_disp_resize_depth, the classes behind the lift, "
      "jp_bev_agree behind both jp_depth_bev_classes and jp_layout_classes_u8, all on one stream.",
      ["jp_depth_bev_lift", "jp_depth_bev_classes", "jp_bev_agree"]),
+    ("Ground plane fitted from depth (csrc/ground.hip; apis/depthbev.py DepthBev(ground=...), PerceptionStream(depth_bev=dict(ground=...))) "
+     "-- the plane jp_depth_bev_lift measures heights against, estimated on the device from the depth map itself and written where the "
+     "lift reads it; no counterpart in the reference (its HEIGHT_FROM_GROUND is a constant).  Every buffer is the caller's (the library "
+     "keeps no state).  jp_ground_fit: depth (B,1,H,W) float metres; layout (B,occ,occ) bytes with the classes of jp_layout_classes_u8, "
+     "or NULL (no road gate); prior (B,4) doubles [nx, ny, nz, h], or NULL; cam (B,8) doubles as for the lift: [0:4] = fx, fy, cx, cy "
+     "are only read, [4:8] = the plane is the RESULT; part (B,parts,10) int64 scratch; mom (B,10) int64; stat (B,3) doubles.  part, mom "
+     "and stat are fully overwritten: the caller zeroes nothing.  One call enqueues `rounds` pairs of launches on `stream`, a moments "
+     "kernel and a solve kernel.  Round 1 gates with `prior`, or with cam[b][4:8] when prior is NULL (tracking: the last result is the "
+     "next prior); later rounds gate with the plane the round before left in cam[b][4:8].  "
+     "MOMENTS, per pixel (u, v) in float64 with every operation rounded once (no fma), in the lift's own order so that X, Y, d and the "
+     "cell carry the same bits as there: (1) d = (double)depth; accept iff d >= min_range && d <= max_range.  (2) X = ((u - cx) / fx) d, "
+     "Y = ((v - cy) / fy) d; accept iff |X| <= max_range && |Y| <= max_range.  (3) r = h - ((nx X + ny Y) + nz d) with the gating "
+     "plane; accept iff r >= -band && r <= band.  (4) with a layout: uu = X / res_f + 0.5 occ, vv = (d + off) / res_f; accept iff "
+     "0 <= uu < occ && 0 <= vv < occ && layout[b][occ - 1 - floor(vv)][floor(uu)] == 1 (road).  Every test is false for NaN and nothing "
+     "is converted to an integer before the test that bounds it has passed.  An accepted pixel is quantised to integer millimetres, "
+     "qx = (long long)floor(X 1000 + 0.5), qy from Y and qz from d likewise, and adds to TEN int64 SUMS in this order: "
+     "[n, sum qx, sum qy, sum qz, sum qx qx, sum qx qz, sum qz qz, sum qx qy, sum qz qy, sum qy qy].  Integer sums are exact and do not "
+     "depend on any order: the table is a pure function of the inputs whatever the grid, the wave order or `parts` (the workgroups per "
+     "camera, each of which stores one row of `part`, ten zeros when it saw no pixel; no atomics, no workgroup waits on another).  "
+     "SOLVE, one workgroup per camera: the rows of part are added in integers and stored to mom[b] = [n, Sx, Sy, Sz, Sxx, Sxz, Szz, Sxy, "
+     "Szy, Syy]; then Y = a X + b Z + c is fitted in float64 with + - x / sqrt only, each rounded once, in exactly this order: "
+     "N = (double)n; mx = Sx / N, my = Sy / N, mz = Sz / N; cxx = Sxx / N - mx mx, cxz = Sxz / N - mx mz, czz = Szz / N - mz mz, "
+     "cxy = Sxy / N - mx my, czy = Szy / N - mz my, cyy = Syy / N - my my; det = cxx czz - cxz cxz; a = (cxy czz - czy cxz) / det; "
+     "b = (czy cxx - cxy cxz) / det; c = my - (a mx + b mz); s = sqrt((a a + 1) + b b); plane = (-a / s, 1 / s, -b / s, (c / 1000) / s); "
+     "e = cyy - (a cxy + b czy); rms = (sqrt(e > 0 ? e : 0) / s) / 1000 (metres).  STATUS CODES, the rules applied in this order: "
+     "1 = too few points: n < min_points (nothing is divided).  2 = ill-conditioned: !(cxx >= sp && czz >= sp && det >= 0.01 (cxx czz)) "
+     "with sp = (1000 min_spread)(1000 min_spread) -- one image row of level ground has czz = 0 and lands here.  3 = out of bounds: a "
+     "component of the plane or rms is not finite, or ny < cos(max_tilt_deg pi / 180) (the host's C library cosine, passed to the "
+     "kernel), or !(h >= h_lo && h <= h_hi).  0 = accepted: the plane is stored to cam[b][4:8].  On any rejection cam[b][4:8] is left as "
+     "it is, except in round 1 of a call that was given `prior`, which copies prior[b] in: cam is then defined by the call alone.  "
+     "stat[b] = [status, n, rms] of the LAST round, rms = NaN unless the status is 0.  Refused before any launch (-1 and a message): "
+     "NULL depth, cam, part, mom or stat; non-positive B, H, W, rounds or parts, parts > 1024, non-positive occ with a layout; "
+     "res_f <= 0; band not greater than zero; max_range not in (0, 1000]; (double)H W (1000 max_range)^2 >= 2^62 (the int64 sums of "
+     "squares could overflow); B H W >= 2^31.  ORDERING in a session: jp_ground_fit behind jp_disp_resize_depth and "
+     "jp_layout_classes_u8 (it reads both outputs), jp_depth_bev_lift behind jp_ground_fit (it reads the plane), all on one stream.",
+     ["jp_ground_fit"]),
     ("KITTI odometry evaluation (csrc/odometry.hip; core/evaluation.py::eval_odometry, apis/inference.py) — the pose chaining of "
      "scripts/draw_odometry.py:62-76 and the numpy toolkit behind the paper's t_err / r_err (mono/tools/kitti_evaluation_toolkit.py:"
      "109-201, mono/tools/geometry.py:20-67, scripts/plot_kitti.py:15-97,223-243).  All arithmetic is double, no atomics: every sum "

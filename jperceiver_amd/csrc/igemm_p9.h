@@ -6,7 +6,7 @@
 // 2-D pixel tile of TR rows x 32 columns; per 32-channel chunk it stages the (TR+2) x 34 input PATCH once -- padding
 // (zero or reflection) resolved while staging -- and all 9 taps read their MFMA B fragments from that patch at a
 // constant LDS offset (dy*PITCH + dx).  The weights (A operand) do not go through LDS at all: they are pre-packed in
-// MFMA fragment order [M tile][quad of 4 k-steps][k parity][row in tile][4] (PACK_FRAG, conv.hip: a workgroup's weight
+// MFMA fragment order [M tile][quad of 4 k-steps][k parity][row in tile][4] (PACK_FRAG, conv_pack.hip: a workgroup's weight
 // stream is one contiguous run, 1 KB per k-step), so a lane's A values for FOUR k-steps are ONE 16-byte global load (L1/L2-resident: every workgroup of an M tile walks the same stream), prefetched a fixed
 // number of k-steps ahead into a register ring.  Per 64 MFMAs a wave therefore issues 32 coalesced weight loads,
 // 2 x 16 ds_read_b32 and ~3 patch loads / LDS stores (vs 32 gathered loads + 32 LDS stores before), and a workgroup

@@ -24,7 +24,7 @@
 //     patch[split][k-half (8 channels)][patch row][column]  = 8 bf16
 // so that a lane's B operand of `v_mfma_f32_32x32x16_bf16` (pixel = lane & 31, 8 consecutive k = channels of k-half
 // lane >> 5) for ANY tap is one aligned ds_read_b128 at a compile-time offset.  The weights are split once per step by the
-// pack (PACK_SPLIT, conv.hip) into MFMA fragment order [M tile][step = (stage, tap, 16-channel group)][split][k-half][row]
+// pack (PACK_SPLIT, conv_pack.hip) into MFMA fragment order [M tile][step = (stage, tap, 16-channel group)][split][k-half][row]
 // x 16 bytes and stream from L2 with one buffer_load_dwordx4 per (row block, split) per step, one step ahead.
 // Per step a wave issues 6 weight loads + 3*NJ LDS reads for 12*NJ MFMAs; a workgroup meets 2 barriers per stage.
 #pragma once

@@ -11,7 +11,7 @@
 //       parity ([even cols | odd cols]) so that a fragment's 32 same-parity pixels are 32 consecutive words;
 //   U stage (32 upsampled channels, 4 slots, 64 k-steps): low-resolution patch 4 x 34 (edge clamp == reflection of up(x));
 //   D stage (the disparity channel, padded to 8: 9 taps x 4 k-pairs = 36 k-steps).
-// Weight pack (PACK_FRAGSEG, conv.hip): [S: M tile][U: class][M tile][D: M tile] streams of quads (4 k-steps x 2 parities
+// Weight pack (PACK_FRAGSEG, conv_pack.hip): [S: M tile][U: class][M tile][D: M tile] streams of quads (4 k-steps x 2 parities
 // x 128 rows x 4 floats = 4 KB); step order inside a stage: (tap | slot, k-pair).
 // Preconditions (host-checked): Cout % 128 == 0, C0 % 32 == 0, C1 % 32 == 0, C2 <= 8, H % 4 == 0, W % 64 == 0.
 #pragma once

@@ -9,7 +9,7 @@
 //       fragment's 32 same-parity pixels are 32 consecutive 16-byte words;
 //   U (upsampled, 4 slots = 4 steps): low-resolution patch 4 x 34 (edge clamp == reflection of up(x));
 //   D (the disparity channel(s), padded to 16: 9 steps).
-// LDS word = 8 channels of one pixel as bf16, [split][k-half][patch row][position]; weights (PACK_SPLITSEG, conv.hip): streams
+// LDS word = 8 channels of one pixel as bf16, [split][k-half][patch row][position]; weights (PACK_SPLITSEG, conv_pack.hip): streams
 // [S: M tile][U: class][M tile][D: M tile] of steps, a step = [split][k-half][128 rows] x 16 bytes, one step ahead.
 //
 // What the round-5 step trace of the round-3 stream showed (profiles/r05_p9us_steps_before.log, cycle stamps per 24-MFMA step):

@@ -176,7 +176,7 @@ def param(p: torch.nn.Parameter) -> Var:
 
 
 # ------------------------------------------------------------------------------------------- packed weights
-# The MFMA convolutions read their weights from a packed copy (csrc/conv.hip "Weight packing").  For weights that are
+# The MFMA convolutions read their weights from a packed copy (csrc/conv_pack.hip "Weight packing").  For weights that are
 # nn.Parameters the copy is PERSISTENT: the first call of a layer packs it and records the pack jobs the library issued;
 # afterwards `PackRegistry.refresh_all()` (called by Baseline.forward) re-packs every layer of the model with ONE
 # kernel launch whenever the weights changed (FlatAdam.step / load_state_dict / .to() bump the epoch, in-place edits of

@@ -65,7 +65,8 @@ __global__ __launch_bounds__(1024) void colsum_kernel(const float* __restrict__ 
 }
 
 // E (B, R, Cn): val[b][j] = max_i E[b][i][j], arg = first argmax (torch.max(dim=1) on CPU/GPU returns
-// an index of a maximal element; ties are measure-zero on real activations)
+// an index of a maximal element; ties are measure-zero on real activations).  NaN propagates as in
+// torch.max and the max-pool kernels: a column that holds a NaN gives val = NaN and arg = the row of its first NaN
 __global__ void colmax_kernel(const float* __restrict__ E, float* __restrict__ val, int64_t* __restrict__ arg,
                               int B, int R, int Cn) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -76,7 +77,7 @@ __global__ void colmax_kernel(const float* __restrict__ E, float* __restrict__ v
     int bi = 0;
     for (int i = 1; i < R; ++i) {
         const float v = e[(size_t)i * Cn];
-        if (v > best) { best = v; bi = i; }
+        if (v > best || (v != v && best == best)) { best = v; bi = i; }
     }
     val[t] = best;
     if (arg) arg[t] = bi;

@@ -391,6 +391,8 @@ def test_area_downsample():
 
 
 # ------------------------------------------------------------------------------------------- small dense / CCT
+# (one shape, fp32 referee: tests/test_dense_f64_gpu.py holds every kernel of small.hip per element to float64 references at ragged
+# tiles, several workgroups, ties, NaN / Inf and seeded accumulation)
 def test_linear_and_cct_algebra():
     B, C, n = 2, 16, 6
     x = rnd(B, 5, 36, seed=1)

@@ -204,7 +204,7 @@ class Perceiver:
 
     def stream(self, src_hw, **kw):
         """A `PerceptionStream` (apis/stream.py) over this model with this Perceiver's output size and depth range: raw uint8
-        camera frames of src_hw = (h, w) pushed one by one; keywords go to the session (cameras, capacity, bev_map, depth_bev, ...)."""
+        camera frames of src_hw = (h, w) pushed one by one; keywords go to the session (cameras, capacity, bev_map, depth_bev, objects, ...)."""
         from .stream import PerceptionStream
         return PerceptionStream(self.model, src_hw, **{**dict(out_size=self.out_size, min_depth=self.min_depth, max_depth=self.max_depth), **kw})
 

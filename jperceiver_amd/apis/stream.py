@@ -41,7 +41,14 @@ depth_bev=dict(K=..., ground=True) (or ground=dict(...), the `ground` argument o
 every frame's depth (and, with use_layout, the road cells of its layout) before the lift measures heights against it.  The order
 of a push becomes jp_layout_classes_u8 -> jp_ground_fit -> jp_depth_bev_lift -> jp_depth_bev_classes -> jp_bev_agree: the lift
 moves behind the layout, in this kind of session only, and every launch still has fixed arguments (the plane travels in device
-memory).  `s.depth_bev.ground()` reads the live plane, its status and the height ratio (the one synchronising step)."""
+memory).  `s.depth_bev.ground()` reads the live plane, its status and the height ratio (the one synchronising step).
+
+objects=True (or a dict of `BevObjects` keyword arguments: max_objects, min_cells, conn, cls, off; apis/bevobj.py): the layout part
+of every push ends with one jp_bev_objects call -- the connected components of the car cells, numbered and measured -- behind
+jp_layout_classes_u8, and in a depth_bev session behind the lift, whose grid it is given (points and height per object).
+`s.objects` is the live `BevObjects`; its `.labels`, `.count` and `.table` are static buffers with the lifetime of the other
+outputs, `s.objects.objects(pose=frame.pose)` is the synchronising read.  `off` defaults from model.opt.split.  The default (None)
+adds nothing to a push."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -70,10 +77,11 @@ class PerceptionStream:
     model.opt's; capacity: trajectory rows kept per camera (later frames still update `pose`); bev_map: None, True or a dict of
     `BevMap` keyword arguments (`off` defaults from model.opt.split, `occ` is the layouts'); depth_bev: None or a dict of
     `DepthBev` keyword arguments with at least K (`off` defaults from model.opt.split; cameras, occ, src_hw, depth_hw and device
-    are the session's)."""
+    are the session's); objects: None, True or a dict of `BevObjects` keyword arguments (`off` defaults from model.opt.split;
+    cameras, occ and device are the session's)."""
 
     def __init__(self, model, src_hw, cameras=1, out_size=None, min_depth=None, max_depth=None, capacity=4096, frozen=True,
-                 bev_map=None, depth_bev=None):
+                 bev_map=None, depth_bev=None, objects=None):
         if not (bev_map is None or bev_map is True or isinstance(bev_map, dict)):
             raise TypeError("bev_map must be None, True or a dict of BevMap keyword arguments")
         if not (depth_bev is None or isinstance(depth_bev, dict)):
@@ -83,6 +91,9 @@ class PerceptionStream:
         if depth_bev is not None and depth_bev.get("ground") is not None:
             from .depthbev import _ground_kw
             _ground_kw(depth_bev["ground"])                           # a malformed `ground` is refused before anything else is looked at
+        if objects is not None:
+            from .bevobj import _objects_kw
+            objects = _objects_kw(objects)                            # ... and so is a malformed `objects`
         if model.training:
             raise RuntimeError("PerceptionStream expects an eval-mode model (call .eval(): BatchNorm must use running stats)")
         p = next(model.parameters())
@@ -123,6 +134,11 @@ class PerceptionStream:
             kw = {"off": 1.9 if getattr(model.opt, "split", None) == "argo" else 0.27, **depth_bev}
             kw.update(cameras=B, occ=int(model.opt.occ_map_size), src_hw=self.src_hw, depth_hw=self.out_size, device=dev)
             self.depth_bev = DepthBev(**kw)
+        self.objects = None                                           # the live BevObjects of an objects session
+        if objects is not None:
+            from .bevobj import BevObjects
+            kw = {"off": 1.9 if getattr(model.opt, "split", None) == "argo" else 0.27, **objects}
+            self.objects = BevObjects(B, int(model.opt.occ_map_size), device=dev, **kw)
 
     # ---------------------------------------------------------------------------------------- state
     def reset(self):
@@ -133,6 +149,8 @@ class PerceptionStream:
             self.bev_map.reset()
         if self.depth_bev is not None:
             self.depth_bev.reset()
+        if self.objects is not None:
+            self.objects.reset()
         self._n = 0
 
     def trajectory(self):
@@ -181,6 +199,10 @@ class PerceptionStream:
                 db._lift(self._depth, False)
             db._classes(False)
             db._agree(self._layout)
+        if self.objects is not None:
+            if (h, w) != (self.objects.occ, self.objects.occ):
+                raise ValueError(f"objects: the layouts are {h} x {w}, model.opt.occ_map_size says {self.objects.occ}")
+            self.objects._find(self._layout, None if db is None else db.grid)      # behind the layout, and behind the lift
         pair = torch.empty((B, 6, _PH, _PW), device=dev)
         # (no magnitude slot: the pose encoder normalises the pair into a new tensor first (ops.affine), and the stem convolution
         # reduces the magnitude of THAT input itself where its kernel reads one -- nothing reads max |pair|)

@@ -268,6 +268,36 @@ GROUPS = [
      "squares could overflow); B H W >= 2^31.  ORDERING in a session: jp_ground_fit behind jp_disp_resize_depth and "
      "jp_layout_classes_u8 (it reads both outputs), jp_depth_bev_lift behind jp_ground_fit (it reads the plane), all on one stream.",
      ["jp_ground_fit"]),
+    ("BEV object instances (csrc/bevobj.hip; apis/bevobj.py BevObjects, PerceptionStream(objects=...)) -- the connected components of one "
+     "class of the layout, numbered and measured on the device; no counterpart in the reference (scripts/eval_kitti_video.py paints the "
+     "car cells blue and stops there).  Every buffer is the caller's (the library keeps no state).  "
+     "jp_bev_objects: layout (B,occ,occ) bytes with the classes of jp_layout_classes_u8; a cell is foreground iff its byte equals "
+     "cls_value (2 = car, 1 = road); conn = 4 or 8 (8: cells that touch at a corner are joined); grid: the (B,4,occ,occ) int32 planes "
+     "[n, n_obst, hmin_mm, hmax_mm] of jp_depth_bev_lift, or NULL.  A component is KEPT iff it has at least min_cells cells; a smaller "
+     "one (an argmax speck) is dropped before numbering: it takes no id and its cells get -1.  ID ORDER: the kept components of a camera "
+     "are numbered 0, 1, 2, ... in raster order of their first cell, the smallest i occ + j.  labels (B,occ,occ) int32: the id of the "
+     "kept component the cell belongs to, -1 for every other cell.  count (B) int32: the number of kept components.  OVERFLOW: count and "
+     "labels are not limited by max_objects -- labels carries the full id even at or above max_objects, count[b] > max_objects tells the "
+     "caller that the table is truncated.  table (B,max_objects,12) int32: row id of camera b describes object id (ids below max_objects "
+     "only), rows at or beyond count[b] are zero.  THE TWELVE FIELDS of a row, in order: [cells, r_min, r_max, c_min, c_max, sum_r, "
+     "sum_c, first_cell, edge_mask, pts, pts_obst, hmax_mm]: the number of cells, the bounding rows and columns (inclusive), the sums of "
+     "the cells' row and column indices (the centroid is sum / cells), first_cell = i occ + j of the first cell in raster order, "
+     "edge_mask bit 0 = touches row 0, bit 1 = row occ-1, bit 2 = column 0, bit 3 = column occ-1 (the object is truncated by the "
+     "layout's window), pts / pts_obst = the sums of the grid's n / n_obst over the object's cells, hmax_mm = the maximum of the grid's "
+     "hmax_mm over the object's cells with n > 0, INT_MIN when there is none; with grid == NULL the last three are 0, 0, INT_MIN.  "
+     "The cell geometry is jp_bev_fuse's: cell (i, j) covers x in [(j - occ/2) res_f, (j + 1 - occ/2) res_f) and z in "
+     "[(occ - 1 - i) res_f - off, (occ - i) res_f - off), res_f = 40 / occ.  Every output is fully overwritten: labels, count, table and "
+     "ws (jp_bev_objects_ws_bytes(B, occ) bytes of caller scratch) need not be initialised.  One call enqueues five launches with "
+     "fixed arguments on `stream` -- wave-local row runs, lock-free atomicMin unions of the remaining links (the root of a component is "
+     "its minimum index whatever the order of arrival; every trip of the union loop lowers an index, so it ends whatever other "
+     "workgroups do), flatten + sizes, one workgroup per camera for the prefix sum of the kept roots in raster order, labels + table "
+     "rows -- a phase that needs a global order is a launch of its own: no workgroup waits on another.  All arithmetic is integer "
+     "(atomicAdd / atomicMin / atomicMax / atomicOr): the result does not depend on any order, two runs give the same bytes.  Refused "
+     "before any launch (-1 and a message): NULL layout, labels, count, table or ws; non-positive B, occ or max_objects; min_cells < 1; "
+     "conn not 4 or 8; cls_value outside 0 .. 255; occ > 1024 (sum_r is an int32: 1024^2 * 1023 < 2^31); B max_objects 12 >= 2^31; "
+     "B occ occ >= 2^31.  ORDERING in a session: jp_bev_objects behind jp_layout_classes_u8, and with a grid behind jp_depth_bev_lift, "
+     "all on one stream.",
+     ["jp_bev_objects_ws_bytes", "jp_bev_objects"]),
     ("KITTI odometry evaluation (csrc/odometry.hip; core/evaluation.py::eval_odometry, apis/inference.py) — the pose chaining of "
      "scripts/draw_odometry.py:62-76 and the numpy toolkit behind the paper's t_err / r_err (mono/tools/kitti_evaluation_toolkit.py:"
      "109-201, mono/tools/geometry.py:20-67, scripts/plot_kitti.py:15-97,223-243).  All arithmetic is double, no atomics: every sum "

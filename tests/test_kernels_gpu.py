@@ -112,6 +112,8 @@ CONV_CASES = [
 ]
 
 
+# (fp32 referee, largest error of the tensor: tests/test_smallconv_f64_gpu.py holds the direct Cout <= 4, disparity-head and 16 -> 16 kernels
+# per element to float64 references on every launch path, scratch tier and ragged channel count)
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv2d_fwd_bwd(case):
     N, Cin, H, W, Cout, K, s, p, pm, act, bias = case
@@ -178,6 +180,8 @@ DISPARITY_HEAD_CASES = [(2, 40, 6, 10), (1, 256, 20, 36), (3, 64, 2, 2), (1, 256
                         (8, 64, 128, 128)]      # large map: the one-chain two-pixel forward, precomputed-gather wgrad
 
 
+# (fp32 referee, largest error of the tensor: tests/test_smallconv_f64_gpu.py holds the direct Cout <= 4, disparity-head and 16 -> 16 kernels
+# per element to float64 references on every launch path, scratch tier and ragged channel count)
 @pytest.mark.parametrize("N,C,h,w", DISPARITY_HEAD_CASES)
 def test_disparity_head_on_upsampled_source(N, C, h, w):
     """disp_k = sigmoid(Conv3x3_reflect(up2x(x))) (depth_decoder.py:36-39,70-71): upsample-aware direct kernels."""
@@ -804,6 +808,8 @@ SMALL_CHANNEL_CASES = [(2, 16, 16, 64, 128, 1, 0, False),    # N, Cin, Cout, H, 
                        (2, 32, 32, 64, 64, 1, 1, True)]       # (32 channels: implicit-GEMM engine)
 
 
+# (fp32 referee, largest error of the tensor: tests/test_smallconv_f64_gpu.py holds the direct Cout <= 4, disparity-head and 16 -> 16 kernels
+# per element to float64 references on every launch path, scratch tier and ragged channel count)
 @pytest.mark.parametrize("N,Cin,Cout,H,W,up,act,bias", SMALL_CHANNEL_CASES)
 def test_small_channel_direct_conv(N, Cin, Cout, H, W, up, act, bias):
     """The 16 / 32-channel 3x3 zero-pad layers of the BEV decoder (layout_model.py:138-153) run on direct VALU kernels

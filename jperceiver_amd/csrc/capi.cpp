@@ -13,7 +13,7 @@ extern "C" int jp_abi_version(void) { return 3; }
 // ---- per-kernel HIP-event timing of the implicit-GEMM launches (bench.py's roofline leg) and of the two element-wise kernels that
 // frozen inference trades for one another, jp_bn_eval_fwd and jp_add_relu (tools/frozen_bench.py; their tag is the entry point's name
 // and their FLOPs are 0, so a consumer that sums GEMM FLOPs is not disturbed by them; neither runs in a train step).
-// Off by default: the launch helpers of conv.hip, conv_wgrad.hip and conv_common.h call jp_prof_before/after, which
+// Off by default: the launch helpers of conv_fwd.hip, conv_dgrad.hip, conv_wgrad.hip, conv_launch.h and conv_common.h call jp_prof_before/after, which
 // return at once unless a profile is open.  jp_profile_begin(n) creates 2n events (host objects, no device memory);
 // while it is open every igemm dispatch is bracketed by two hipEventRecord calls ON THE STREAM IT IS LAUNCHED ON, so the timings are valid with
 // the side stream running (torch.cuda.Event only sees torch's current stream).  Single-threaded by design.

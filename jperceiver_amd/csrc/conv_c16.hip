@@ -199,7 +199,7 @@ int launch_conv(const float* x, const float* w, const float* bias, float* y, int
 
 }  // namespace
 
-// internal entry points used by the dispatchers of conv.hip and conv_wgrad.hip (prototypes in conv_common.h; not part of the public ABI)
+// internal entry points used by the dispatchers of conv_fwd.hip, conv_dgrad.hip and conv_wgrad.hip (prototypes in conv_common.h; not part of the public ABI)
 bool jp_c16_ok(int Cin, int Cout, int KH, int stride, int pad, int pad_mode, int H, int W) {
     static const bool on = [] { const char* e = getenv("JP_C16"); return !(e && e[0] == '0'); }();
     // 16 -> 16 only: measured at 8 x 32 x 128^2 the 32-channel instantiations lose to the implicit-GEMM engine (forward 32 -> 32

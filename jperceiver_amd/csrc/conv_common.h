@@ -1,6 +1,7 @@
-// What conv.hip (forward, dgrad) and conv_wgrad.hip share: the source descriptor, the pixel decode and generic gather, the scratch
+// What conv_fwd.hip, conv_dgrad.hip and conv_wgrad.hip share: the source descriptor, the pixel decode and generic gather, the scratch
 // epilogue of the split-K launches, the launch helpers of the generic engine, and the prototypes of conv_small.hip / conv_c16.hip.
-// In an anonymous namespace or inline, as in conv.hip before the cut; not part of the ABI.  conv.hip's head has the GEMM shapes.
+// In an anonymous namespace or inline, as in the single unit these were cut from; not part of the ABI.  conv_fwd.hip's head has the
+// GEMM shapes; what only forward and dgrad share (the patch-kernel launch layer) is in conv_launch.h.
 #pragma once
 #include "igemm.h"
 #include "scale.h"

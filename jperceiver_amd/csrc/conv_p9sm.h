@@ -1,4 +1,5 @@
-// Small-map split-bf16 patch launches (conv_p9sm.hip): plan + launch, called by conv.hip's dispatcher (not part of the ABI).
+// Small-map split-bf16 patch launches (conv_p9sm.hip): plan + launch, called by the dispatchers of conv_fwd.hip and
+// conv_dgrad.hip, chosen by p9sm_wanted of conv_launch.h (not part of the ABI).
 #pragma once
 #include "jp_common.h"
 #include "scale.h"

@@ -5,8 +5,8 @@
 //   * partial tiles are masked (zeros staged outside the map, stores only inside), and
 //   * the reduction (16-channel stages) is split over grid.z when there are fewer than ~192 tiles; every slice writes its
 //     partial tile to caller scratch part[slice][m][pixel] and the caller folds the slices in a fixed order
-//     (slice_reduce_nchw_kernel, conv.hip) -- bit-reproducible, no atomics.
-// Same weight pack as P9S (PACK_SPLIT fragment order, pack_p9 in conv.hip).  JP_P9SM=0 turns the path off.
+//     (slice_reduce_nchw_kernel, conv_fwd.hip) -- bit-reproducible, no atomics.
+// Same weight pack as P9S (PACK_SPLIT fragment order, pack_p9 in conv_launch.h).  JP_P9SM=0 turns the path off.
 #include <algorithm>
 #include <cstdlib>
 

@@ -1,6 +1,7 @@
-// Weight packing of the conv2d dispatchers (conv_pack.hip): the pack modes and the two functions through which conv.hip
-// issues a pack.  The recorder behind them (jp_pack_record_begin / _end) and the one-launch replay
-// (jp_pack_replay) are ABI entry points of conv_pack.hip; these two are internal (hidden visibility).
+// Weight packing of the conv2d dispatchers (conv_pack.hip): the pack modes and the two functions through which the dispatchers
+// (conv_fwd.hip, conv_dgrad.hip, conv_wgrad.hip; pack_p9 of conv_launch.h) issue a pack.  The recorder behind them
+// (jp_pack_record_begin / _end) and the one-launch replay (jp_pack_replay) are ABI entry points of conv_pack.hip; these two are
+// internal (hidden visibility).
 #pragma once
 #include "jp_common.h"
 

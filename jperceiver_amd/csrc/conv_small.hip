@@ -595,7 +595,7 @@ __global__ void up_head_wgrad_fold_kernel(const float* __restrict__ part, float*
 
 }  // namespace
 
-// internal entry points used by the dispatchers of conv.hip and conv_wgrad.hip (prototypes in conv_common.h; not part of the public ABI)
+// internal entry points used by the dispatchers of conv_fwd.hip, conv_dgrad.hip and conv_wgrad.hip (prototypes in conv_common.h; not part of the public ABI)
 int jp_conv_small_fwd(const float* x0, int c0, int up0, const float* x1, int c1, int up1, const float* x2, int c2, int up2,
                       const float* w, const float* bias, float* y, int N, int H, int W, int Cout, int act, int reflect,
                       hipStream_t st, int accumulate) {

@@ -1,5 +1,5 @@
 // conv2d wgrad: jp_conv2d_wgrad[_src3], their scratch-size queries, the split-K plans and the reduce / fold kernels, and the loaders
-// and epilogues that only wgrad instantiates (conv.hip's head has the GEMM shapes and the loader families).
+// and epilogues that only wgrad instantiates (conv_fwd.hip's head has the GEMM shapes and the loader families).
 // igemm_w9.h, igemm_w9s.h and igemm_w9s2.h define non-template kernels: they are included here and nowhere else.
 #include "conv_common.h"
 #include "igemm_w9s.h"
@@ -7,7 +7,7 @@
 #include "igemm_w4s.h"
 #include "igemm_w9.h"
 #include "igemm_w7.h"
-constexpr double JP_NPROD = JP_NS == 2 ? 3.0 : 6.0;     // matrix-pipe products per fp32 product of the W9S-family kernels (as in conv.hip)
+constexpr double JP_NPROD = JP_NS == 2 ? 3.0 : 6.0;     // matrix-pipe products per fp32 product of the W9S-family kernels (as in conv_launch.h)
 
 namespace {
 

@@ -1,6 +1,6 @@
 // One LDS-staged fp32-MFMA implicit-GEMM engine for gfx950:  C[m][n] (+)= sum_k A(m,k) * B(k,n)
 // with pluggable gather-loaders for A and B and a pluggable epilogue.  conv2d forward, dgrad and
-// wgrad and the 1x1 convs are all instances of this kernel (conv.hip, conv_wgrad.hip).
+// wgrad and the 1x1 convs are all instances of this kernel (conv_fwd.hip, conv_dgrad.hip, conv_wgrad.hip).
 //
 // Geometry: 4 or 8 wave64 per workgroup.  Every wave owns a 64x64 output tile as 2x2
 // v_mfma_f32_32x32x2_f32 accumulators (exact fp32, 64 FLOP/clk/SIMD = the fp32 peak, guide

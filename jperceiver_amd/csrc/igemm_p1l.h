@@ -21,7 +21,7 @@
 // Tile: 8 waves = 4 channel blocks (wm) x 2 pixel-row pairs (wn); wave = 64 channels x 2 rows x 32 pixels (same as the patch
 // kernel: same products in the same order, bit-identical results).  LDS: 2 x 24 KB patch + 2 x 48 KB weights = 144 KB.
 // Preconditions (host-checked): M % 256 == 0, C % 128 == 0 (stages of 32 channels, in fours), H % 4 == 0, W % 32 == 0, N*C*H*W*4 < 2^31; pack = PACK_SPLIT with
-// 256-row tiles and KGS = 2 (conv.hip: p9s_ws_floats).
+// 256-row tiles and KGS = 2 (conv_launch.h: p9s_ws_floats).
 #pragma once
 #include "igemm_p9s.h"
 #ifdef P1L_TRACE

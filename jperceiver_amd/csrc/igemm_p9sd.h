@@ -1,6 +1,6 @@
 // "P9SD" patch kernel: dgrad of the UPSAMPLED segment of an iconv layer, directly at half resolution, on the bf16 matrix pipe
 // (split products, igemm_p9s.h).  With y = Conv3x3_reflect(cat(.., up2x(x), ..)) an output pixel (2i'+a, 2j'+b) of parity class
-// (a, b) sees a 2x2 patch of x through 4 pre-summed weight slots W'_{ab}[r][s] (conv.hip, "parity-class form"), hence
+// (a, b) sees a 2x2 patch of x through 4 pre-summed weight slots W'_{ab}[r][s] (conv_fwd.hip, "parity-class form"), hence
 //     dX[c][i][j] = sum_{class (a,b), slot (r,s), co}  W'_{ab}[r][s][co][c] * dY[co][2i + 2 - a - 2r][2j + 2 - b - 2s]
 // (zero where the dY index leaves the image; the edge-clamp fold is DgradUPBorderB's pass): a 16-"tap" correlation over the
 // FULL-resolution dY, sampled at stride 2.  GEMM M = c, N = half-resolution pixels, K = (16-channel stage of co, 16 (class,

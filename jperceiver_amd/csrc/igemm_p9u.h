@@ -1,5 +1,5 @@
 // "P9U" patch kernel: the decoder's iconv layers  y = act(Conv3x3_reflect(cat(skip, up2x(x), disp)) + b)
-// (depth_decoder.py:76-77) on the fp32 MFMA pipe, in the parity-class form of conv.hip (an output pixel (2i+a, 2j+b)
+// (depth_decoder.py:76-77) on the fp32 MFMA pipe, in the parity-class form of conv_fwd.hip (an output pixel (2i+a, 2j+b)
 // sees only a 2x2 patch of x through its 9 taps, against weights pre-summed per class (a, b): 4 "slots" instead of 9 taps
 // on the upsampled segment) with the P9 machinery: operands staged once per 32-channel stage for all taps / slots, the
 // weights streamed from L2 in MFMA fragment order as 16-byte buffer loads, no address arithmetic in the k loop.

@@ -9,12 +9,32 @@ PyTorch supplies device memory (caching allocator), streams and nn.Module/state_
 """
 from __future__ import annotations
 
+import atexit
+import collections
+import ctypes as _ct
+import functools
+import os as _os
+import traceback
+import weakref
+
+import numpy as np
 import torch
 
 from ._lib import call, lib as _jplib
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
 PAD_ZERO, PAD_REFLECT = 0, 1
+
+
+def _q(name, *ints) -> int:
+    """A host-side query of the library (scratch sizes, route predicates, constants): no launch, no device access."""
+    return int(_jplib().fn[name](*ints))
+
+
+@functools.lru_cache(maxsize=None)
+def _lib_const(name) -> int:
+    """An integer constant of the loaded library, asked once per process."""
+    return _q(name)
 
 
 # ------------------------------------------------------------------------------------------- tape
@@ -112,7 +132,6 @@ def grad_ready(tag: str):
 
 
 # ---- companion streams for parameter-gradient kernels (JP_WGRAD_STREAM=0 turns them off)
-import os as _os
 _WG_ON = _os.environ.get("JP_WGRAD_STREAM", "1") != "0"
 _WG_STREAMS = {}
 _WG_ACTIVE = [False]
@@ -181,10 +200,6 @@ def param(p: torch.nn.Parameter) -> Var:
 # afterwards `PackRegistry.refresh_all()` (called by Baseline.forward) re-packs every layer of the model with ONE
 # kernel launch whenever the weights changed (FlatAdam.step / load_state_dict / .to() bump the epoch, in-place edits of
 # a parameter are caught through its version counter), and the conv entry points run with ws_state=1.
-import weakref
-
-import numpy as np
-
 _JOB_DT = np.dtype([("w", "u8"), ("wp", "u8"), ("total", "i8"), ("begin", "i8"), ("mode", "i4"), ("p", "i4", (6,)),
                     ("pad", "i4")])
 _EPOCH = [0]
@@ -212,7 +227,7 @@ class PackRegistry:
     _by_device = {}
 
     def __init__(self, device):
-        assert int(_jplib().fn["jp_pack_job_bytes"]()) == _JOB_DT.itemsize
+        assert _q("jp_pack_job_bytes") == _JOB_DT.itemsize
         self.device = device
         self.entries = {}
         self.table = None            # (device jobs tensor, njobs, total elements)
@@ -338,14 +353,9 @@ def _conv_call(name, w: Var, which: str, sig, nfloats: int, args_before_ws, args
 
 # ---- operand scales of the fp16 two-way split kernels (csrc/scale.hip): a tensor's largest magnitude is reduced ONCE and handed to
 # every convolution call that reads the tensor (forward + weight gradient for an activation, dgrad + weight gradient for a gradient)
-_SPLIT_SCHEME = []
-
-
 def split_scheme() -> int:
     """2: the library's patch kernels use two fp16 splits per operand (three products), 3: three bf16 splits (six products)."""
-    if not _SPLIT_SCHEME:
-        _SPLIT_SCHEME.append(int(_jplib().fn["jp_split_scheme"]()))
-    return _SPLIT_SCHEME[0]
+    return _lib_const("jp_split_scheme")
 
 
 def _amax_of(v) -> torch.Tensor | None:
@@ -359,18 +369,14 @@ def _amax_of(v) -> torch.Tensor | None:
     out = _amax_slot(v.device)
     call("jp_amax_into", v, v.numel(), out)
     if _AMAX_LOG is not None:
-        import traceback
         fr = [f for f in traceback.extract_stack(limit=12) if "ops.py" not in f.filename]
         key = (tuple(v.shape), fr[-1].name + ":" + str(fr[-1].lineno) if fr else "?")
         _AMAX_LOG[key] = _AMAX_LOG.get(key, 0) + 1
     return out
 
 
-import os as _os
 _AMAX_LOG = {} if _os.environ.get("JP_AMAX_LOG") else None
 if _AMAX_LOG is not None:
-    import atexit
-
     def _dump():
         rows = sorted(_AMAX_LOG.items(), key=lambda kv: -kv[1] * int(np.prod(kv[0][0])))
         tot = sum(c * int(np.prod(k[0])) * 4 for k, c in rows)
@@ -404,13 +410,8 @@ def _amax_slot(dev) -> torch.Tensor:
     return ent[0][(ent[1] - 1) * SF:ent[1] * SF]
 
 
-_SLOT_FLOATS = []
-
-
 def _slot_floats() -> int:
-    if not _SLOT_FLOATS:
-        _SLOT_FLOATS.append(int(_jplib().fn["jp_amax_slot_floats"]()))
-    return _SLOT_FLOATS[0]
+    return _lib_const("jp_amax_slot_floats")
 
 
 def _amax_ws(dev, *amaxes):
@@ -428,13 +429,8 @@ def _amax_ws(dev, *amaxes):
     return ent[0]
 
 
-_WS_SLOTS = []
-
-
 def _ws_slots() -> int:
-    if not _WS_SLOTS:
-        _WS_SLOTS.append(int(_jplib().fn["jp_conv2d_amax_ws_floats"]()) // _slot_floats())
-    return _WS_SLOTS[0]
+    return _lib_const("jp_conv2d_amax_ws_floats") // _slot_floats()
 
 
 def _out_slot(dev, on=True):
@@ -442,12 +438,9 @@ def _out_slot(dev, on=True):
     return _amax_slot(dev) if (on and split_scheme() == 2) else None
 
 
-import ctypes as _ct
-
-
 def _ws_floats(Cin, Cout, KH, which):
     """Caller-owned packed-weight scratch of the conv fast path (jp_conv2d_ws_floats)."""
-    return int(_jplib().fn["jp_conv2d_ws_floats"](Cin, Cout, KH, which))
+    return _q("jp_conv2d_ws_floats", Cin, Cout, KH, which)
 
 
 def _pad32(c):
@@ -458,7 +451,91 @@ def _new(shape, like: torch.Tensor, dtype=None):
     return torch.empty(shape, device=like.device, dtype=dtype or like.dtype)
 
 
+def _gather_channels(parts, dst):
+    """Write the (Var, upsampled?) parts side by side into channel slices of `dst` (N, sum of their channels, H, W)."""
+    N, Ct, H, W = dst.shape
+    c0 = 0
+    for v, u in parts:
+        C = v.t.shape[1]
+        if u:
+            call("jp_upsample2x_fwd", v.t, dst, N, C, H // 2, W // 2, Ct, c0)
+        else:
+            call("jp_copy_channels", v.t, dst, N, C, H * W, C, 0, Ct, c0, 0)
+        c0 += C
+
+
+def _scatter_channels(src, parts):
+    """The adjoint: add (or write, Var.grad_buf) the channel slices of `src` into the gradient buffers of the parts that need one."""
+    N, Ct, H, W = src.shape
+    c0 = 0
+    for v, u in parts:
+        C = v.t.shape[1]
+        if v.rg:
+            g, acc = v.grad_buf()
+            if u:
+                call("jp_upsample2x_bwd", src, g, N, C, H // 2, W // 2, Ct, c0, acc)
+            else:
+                call("jp_copy_channels", src, g, N, C, H * W, Ct, c0, C, 0, acc)
+        c0 += C
+
+
 # ------------------------------------------------------------------------------------------- conv
+class _ConvGeom(collections.namedtuple("_ConvGeom", "cs ups nsrc N H W Cin Cout KH stride pad pad_mode OH OW")):
+    """One convolution layer as the library's host-side queries see it: no tensors, nothing of the device.  cs, ups: channels and
+    upsample flag (1: stored at half resolution, read through the nearest-2x upsample) of the three source slots, 0 where a slot is
+    unused; nsrc: slots in use."""
+    __slots__ = ()
+    cu = property(lambda g: tuple(a for cu in zip(g.cs, g.ups) for a in cu))                # (c0, up0, c1, up1, c2, up2) of the *_src3* queries
+    big = property(lambda g: g.Cin >= 32 and g.Cout >= 32)                                  # (few-channel layers: direct kernels, no operand scales)
+    single = property(lambda g: g.nsrc == 1 and not g.ups[0])                               # one source, at full resolution
+    sig = property(lambda g: (g.cs, g.ups, g.N, g.H, g.W, g.stride, g.pad, g.pad_mode))     # key of the layer's persistent weight packs
+
+    def concat(self):
+        """the same layer on its sources materialised into one (N, Cin, H, W) tensor"""
+        return self._replace(cs=(self.Cin, 0, 0), ups=(0, 0, 0), nsrc=1)
+
+
+def _src3_args(ts, g: _ConvGeom):
+    """(x0, c0, up0, x1, c1, up1, x2, c2, up2): the source arguments of the *_src3 entry points"""
+    return [a for xcu in zip(ts, g.cs, g.ups) for a in xcu]
+
+
+def _wgrad_route(g: _ConvGeom):
+    """-> ("direct" | "concat", floats of scratch) for jp_conv2d_wgrad_src3.  direct: on the sources as they are; concat: on the
+    sources materialised into one tensor (geometry g.concat()).  Host-side queries only."""
+    if not g.single:
+        n = _q("jp_conv2d_wgrad_src3_ws_floats", *g.cu, g.N, g.H, g.W, g.Cout, g.KH, g.stride, g.pad, g.pad_mode)
+        if g.nsrc == 1 and _q("jp_conv2d_up_head_ok", g.cs[0], g.ups[0], 0, 0, g.Cout, g.KH, g.stride, g.pad, g.pad_mode, g.H, g.W):
+            # disparity head on an upsampled source: upsample-aware direct kernel, nothing materialised
+            # (16 gathered dY sums per half-resolution pixel + the workgroups' partial sums, folded in a fixed order)
+            return "direct", n
+        if g.nsrc > 1 and n:
+            # per-segment wgrad inside the library: full-resolution segments from their own tensors, the upsampled one in
+            # parity-class form -- no materialised concat.  (Asked for several sources only: one upsampled 64-channel source
+            # gets a positive answer too and still goes on to the concat.)
+            return "direct", n
+        if g.Cin < 32:
+            # few-channel layer on an upsampled source (BEV decoder 16 -> 16): partial sums of the direct kernel
+            return "direct", n
+    # one full-resolution source -- or made one: materialise the virtual upsample+concat once, the single-source wgrad gather is ~2x faster
+    return ("direct" if g.single else "concat"), _q("jp_conv2d_wgrad_ws_floats", g.N, g.Cin, g.H, g.W, g.Cout, g.KH, g.stride, g.pad)
+
+
+def _dgrad_route(g: _ConvGeom):
+    """-> ("single" | "src3" | "concat", floats of the packed weights, floats of split-K scratch).  single: jp_conv2d_dgrad into the
+    source's gradient buffer; src3: jp_conv2d_dgrad_src3 into each source's; concat: jp_conv2d_dgrad into a buffer of the virtual
+    concat, routed to the sources afterwards.  Host-side queries only."""
+    pack = _ws_floats(g.Cin, g.Cout, g.KH, 1) if g.Cout >= 16 else 0
+    if not g.single and _q("jp_conv2d_dgrad_src3_ok", *g.cu, g.N, g.H, g.W, g.Cout, g.KH, g.stride, g.pad, g.pad_mode):
+        # per-source dgrad inside the library: straight into each source's gradient buffer, the upsampled source at its own
+        # (half) resolution
+        return "src3", pack, _q("jp_conv2d_dgrad_src3_split_floats", *g.cu, g.N, g.H, g.W)
+    # (concat: split-K scratch as in the single-source call: small-grid layers then fold their K slices in a fixed order instead of
+    # meeting in fp32 atomics)
+    return ("single" if g.single else "concat"), pack, _q("jp_conv2d_dgrad_split_floats", g.N, g.Cin, g.H, g.W, g.Cout, g.KH,
+                                                          g.stride, g.pad)
+
+
 def conv2d(x, w: Var, b: Var | None, stride=1, pad=0, pad_mode=PAD_ZERO, act=ACT_NONE, srcs=None, bn_stats=False) -> Var:
     """nn.Conv2d (+ReflectionPad2d, +bias, +activation epilogue).  `srcs` = [(Var, upsampled?)...] (<=3)
     feeds the conv with the channel-concat of the sources, half-resolution ones being read through a
@@ -476,19 +553,16 @@ def conv2d(x, w: Var, b: Var | None, stride=1, pad=0, pad_mode=PAD_ZERO, act=ACT
     OH = (H + 2 * pad - KH) // stride + 1
     OW = (W + 2 * pad - KH) // stride + 1
     y = _new((N, Cout, OH, OW), w.t)
-    s3 = []
-    for i in range(3):
-        if i < len(srcs):
-            s3 += [srcs[i][0].t, srcs[i][0].t.shape[1], srcs[i][1]]
-        else:
-            s3 += [None, 0, 0]
+    fill = (0,) * (3 - len(srcs))
+    geom = _ConvGeom(tuple(v.t.shape[1] for v, _ in srcs) + fill, tuple(u for _, u in srcs) + fill, len(srcs),
+                     N, H, W, Cin, Cout, KH, stride, pad, pad_mode, OH, OW)
+    ts = tuple(v.t for v, _ in srcs) + (None,) * len(fill)
+    sig, big = geom.sig, geom.big
     bt = b.t if b is not None else None
     # scratch for the packed-weight (tap-major) fast path; None -> generic path (few reduction channels)
     nwf = _ws_floats(Cin, Cout, KH, 0)
-    nsp = int(_jplib().fn["jp_conv2d_fwd_split_floats"](N, Cin, H, W, Cout, KH, stride, pad))
+    nsp = _q("jp_conv2d_fwd_split_floats", N, Cin, H, W, Cout, KH, stride, pad)
     ws_s = _new((nsp,), w.t) if nsp else None      # fixed-order split-K reduction of small-grid layers
-    sig = (tuple(s3[1::3]), tuple(s3[2::3]), N, H, W, stride, pad, pad_mode)
-    big = Cin >= 32 and Cout >= 32            # (the few-channel layers run direct kernels without operand scales)
     # operand magnitudes of the fp16 split kernels (explicit arguments of the entry points, include/jperceiver_hip.h): one slot per
     # source, reduced once per tensor (_amax_of) or reported by its producer; the few-channel layers leave it to the library
     x_am = [(_amax_of(srcs[i][0]) if (big and i < len(srcs)) else None) for i in range(3)]
@@ -498,9 +572,9 @@ def conv2d(x, w: Var, b: Var | None, stride=1, pad=0, pad_mode=PAD_ZERO, act=ACT
     # y^2 in `st_ws` (their epilogue), and BatchNorm folds those instead of reading y once more
     st_ws, st_parts = None, _ct.c_int(0)
     if bn_stats and big and KH == 3 and stride == 1 and bt is None and act == ACT_NONE and len(srcs) == 1:
-        st_ws = _new((int(_jplib().fn["jp_conv2d_fwd_bn_stats_floats"](N, OH, OW, Cout)),), w.t)
+        st_ws = _new((_q("jp_conv2d_fwd_bn_stats_floats", N, OH, OW, Cout),), w.t)
     _conv_call("jp_conv2d_fwd_src3", w, "fwd", sig, nwf,
-               (*s3, w.t, bt, y, N, H, W, Cout, KH, stride, pad, pad_mode, act),
+               (*_src3_args(ts, geom), w.t, bt, y, N, H, W, Cout, KH, stride, pad, pad_mode, act),
                (ws_s, *x_am, y_slot, _ct.addressof(y_done),
                 _amax_ws(y.device, *(x_am[:len(srcs)] if len(srcs) == 1 else (None,))),      # (several sources: their slots are folded into the scratch)
                 st_ws, _ct.addressof(st_parts)))
@@ -521,7 +595,7 @@ def conv2d(x, w: Var, b: Var | None, stride=1, pad=0, pad_mode=PAD_ZERO, act=ACT
             ao = _out_slot(dy.device, big)
             if b is not None and b.rg and Cout <= 65535:
                 # activation backward and bias gradient in one pass (the bias gradient is a sum over the tensor this pass writes)
-                nbw = int(_jplib().fn["jp_act_bwd_bias_ws_floats"](N, Cout, OH * OW))
+                nbw = _q("jp_act_bwd_bias_ws_floats", N, Cout, OH * OW)
                 call("jp_act_bwd_bias", dy, y, d2, b.g, N, Cout, OH * OW, act, ao, _new((nbw,), dy))    # (scratch: fixed-order fold)
                 bias_done = True
             else:
@@ -535,56 +609,20 @@ def conv2d(x, w: Var, b: Var | None, stride=1, pad=0, pad_mode=PAD_ZERO, act=ACT
 
         def param_grads():
             if b is not None and b.rg and not bias_done:
-                ncw = int(_jplib().fn["jp_channel_sum_ws_floats"](N, Cout, OH * OW))
+                ncw = _q("jp_channel_sum_ws_floats", N, Cout, OH * OW)
                 call("jp_channel_sum", dy, b.g, N, Cout, OH * OW, 1, _new((ncw,), dy))
             if w.rg:
-                wg_am = (*x_am, dy_am, _amax_ws(dy.device, dy_am, *x_am[:len(srcs)]))
-                nms = 0
-                if len(srcs) > 1:
-                    nms = int(_jplib().fn["jp_conv2d_wgrad_src3_ws_floats"](s3[1], s3[2], s3[4], s3[5], s3[7], s3[8], N, H, W, Cout,
-                                                                             KH, stride, pad, pad_mode))
-                up_head = len(srcs) == 1 and srcs[0][1] and int(_jplib().fn["jp_conv2d_up_head_ok"](
-                    s3[1], s3[2], 0, 0, Cout, KH, stride, pad, pad_mode, H, W))
-                if up_head:     # disparity head on an upsampled source: upsample-aware direct kernel, nothing materialised
-                    # 16 gathered dY sums per half-resolution pixel + the workgroups' partial sums (folded in a fixed order)
-                    nup = int(_jplib().fn["jp_conv2d_wgrad_src3_ws_floats"](s3[1], s3[2], 0, 0, 0, 0, N, H, W, Cout, KH, stride, pad,
-                                                                             pad_mode))
-                    ws_w = _new((nup,), dy)
-                    call("jp_conv2d_wgrad_src3", *s3, dy, w.g, N, H, W, Cout, KH, stride, pad, pad_mode, 1, ws_w, nup, *wg_am)
-                    del ws_w
-                elif nms:
-                    # per-segment wgrad inside the library: full-resolution segments from their own tensors, the
-                    # upsampled one in parity-class form -- no materialised concat
-                    ws_w = _new((nms,), dy)
-                    call("jp_conv2d_wgrad_src3", *s3, dy, w.g, N, H, W, Cout, KH, stride, pad, pad_mode, 1, ws_w, nms, *wg_am)
-                    del ws_w
-                elif (len(srcs) > 1 or srcs[0][1]) and Cin >= 32:
-                    # materialise the virtual upsample+concat once: the single-source wgrad gather is ~2x faster
-                    xc = _new((N, Cin, H, W), dy)
-                    c0 = 0
-                    for v, u in srcs:
-                        C = v.t.shape[1]
-                        if u:
-                            call("jp_upsample2x_fwd", v.t, xc, N, C, H // 2, W // 2, Cin, c0)
-                        else:
-                            call("jp_copy_channels", v.t, xc, N, C, H * W, C, 0, Cin, c0, 0)
-                        c0 += C
-                    nws = int(_jplib().fn["jp_conv2d_wgrad_ws_floats"](N, Cin, H, W, Cout, KH, stride, pad))
-                    ws_w = _new((nws,), dy) if nws else None
+                wg, xs, wg_am = geom, ts, (*x_am, dy_am, _amax_ws(dy.device, dy_am, *x_am[:len(srcs)]))
+                kind, nws = _wgrad_route(geom)
+                if kind == "concat":
+                    wg, xs = geom.concat(), (_new((N, Cin, H, W), dy), None, None)
+                    _gather_channels(srcs, xs[0])
                     # (the concatenated copy's magnitude = the largest of its sources': the library folds the slots)
-                    call("jp_conv2d_wgrad_src3", xc, Cin, 0, None, 0, 0, None, 0, 0, dy, w.g, N, H, W, Cout, KH, stride, pad,
-                         pad_mode, 1, ws_w, nws, None, None, None, dy_am, _amax_ws(dy.device, None))
-                    del xc, ws_w
-                else:
-                    single = len(srcs) == 1 and not srcs[0][1]
-                    if single:
-                        nws = int(_jplib().fn["jp_conv2d_wgrad_ws_floats"](N, Cin, H, W, Cout, KH, stride, pad))
-                    else:       # few-channel layer on an upsampled source (BEV decoder 16 -> 16): partial sums of the direct kernel
-                        nws = int(_jplib().fn["jp_conv2d_wgrad_src3_ws_floats"](s3[1], s3[2], s3[4], s3[5], s3[7], s3[8], N, H, W,
-                                                                                 Cout, KH, stride, pad, pad_mode))
-                    ws_w = _new((nws,), dy) if nws else None
-                    call("jp_conv2d_wgrad_src3", *s3, dy, w.g, N, H, W, Cout, KH, stride, pad, pad_mode, 1, ws_w, nws, *wg_am)
-                    del ws_w
+                    wg_am = (None, None, None, dy_am, _amax_ws(dy.device, None))
+                ws_w = _new((nws,), dy) if nws else None
+                call("jp_conv2d_wgrad_src3", *_src3_args(xs, wg), dy, w.g, N, H, W, Cout, KH, stride, pad, pad_mode, 1, ws_w, nws,
+                     *wg_am)
+                del xs, ws_w
 
         # Parameter gradients are off the critical path (nothing in the backward chain reads them): they run on a
         # companion stream of the tape's stream, so the wgrad kernels fill the CUs that the dgrad chain's kernel tails
@@ -605,32 +643,11 @@ def conv2d(x, w: Var, b: Var | None, stride=1, pad=0, pad_mode=PAD_ZERO, act=ACT
                     a.record_stream(wgs)
         if any(v.rg for v, _ in srcs):
             dg_am = (dy_am, _amax_ws(dy.device, dy_am))
-            nwd = _ws_floats(Cin, Cout, KH, 1) if Cout >= 16 else 0
-            if len(srcs) == 1 and srcs[0][1] == 0:
-                g, acc = srcs[0][0].grad_buf()
-                nsd = int(_jplib().fn["jp_conv2d_dgrad_split_floats"](N, Cin, H, W, Cout, KH, stride, pad))
-                ws_s = _new((nsd,), dy) if nsd else None
-                dx_slot, dx_done = _out_slot(dy.device, big), _ct.c_int(0)
-                _conv_call("jp_conv2d_dgrad", w, "dgrad", sig, nwd,
-                           (dy, w.t, g, N, Cin, H, W, Cout, KH, stride, pad, pad_mode, acc),
-                           (ws_s, dg_am[0], dx_slot, _ct.addressof(dx_done), dg_am[1]))
-                del ws_s
-                if dx_done.value:         # max |dx| out of the dgrad epilogue (+ border fold): the scale of the next convolution backward
-                    srcs[0][0].gamax = dx_slot
-            elif int(_jplib().fn["jp_conv2d_dgrad_src3_ok"](s3[1], s3[2], s3[4], s3[5], s3[7], s3[8], N, H, W, Cout, KH,
-                                                           stride, pad, pad_mode)):
-                # per-source dgrad inside the library: straight into each source's gradient buffer, the upsampled
-                # source at its own (half) resolution
-                ga = []
-                for i in range(3):
-                    if i < len(srcs) and srcs[i][0].rg:
-                        g, acc = srcs[i][0].grad_buf()
-                        ga += [g, s3[3 * i + 1], s3[3 * i + 2], acc]
-                    else:
-                        ga += [None, s3[3 * i + 1], s3[3 * i + 2], 0]
-                rgs = tuple(ga[0::4][i] is not None for i in range(3))
-                nsd = int(_jplib().fn["jp_conv2d_dgrad_src3_split_floats"](*[v for i in range(3) for v in (s3[3 * i + 1], s3[3 * i + 2])],
-                                                                          N, H, W))
+            kind, nwd, nsd = _dgrad_route(geom)
+            if kind == "src3":
+                rgs = tuple(bool(v.rg) for v, _ in srcs) + (False,) * len(fill)
+                bufs = [srcs[i][0].grad_buf() if need else (None, 0) for i, need in enumerate(rgs)]
+                ga = [a for (gx, acc), c, u in zip(bufs, geom.cs, geom.ups) for a in (gx, c, u, acc)]
                 ws_s = _new((nsd,), dy) if nsd else None
                 dx_slot, dx_done = _out_slot(dy.device, big and rgs[0]), _ct.c_int(0)
                 _conv_call("jp_conv2d_dgrad_src3", w, "dgrad3", sig + rgs, nwd,
@@ -639,25 +656,20 @@ def conv2d(x, w: Var, b: Var | None, stride=1, pad=0, pad_mode=PAD_ZERO, act=ACT
                 del ws_s
                 if dx_done.value:         # (the first source's gradient as STORED -- also when the call accumulated into it)
                     srcs[0][0].gamax = dx_slot
-            else:   # gradient w.r.t. the virtual concat, then routed to the sources
-                dcat = _new((N, Cin, H, W), dy)
-                # (split-K scratch as in the single-source call: small-grid layers then fold their K slices in a fixed order
-                # instead of meeting in fp32 atomics)
-                nsd = int(_jplib().fn["jp_conv2d_dgrad_split_floats"](N, Cin, H, W, Cout, KH, stride, pad))
+            else:
+                # single: into the source's gradient buffer; concat: the gradient w.r.t. the virtual concat, then routed to the sources
+                x0 = srcs[0][0] if kind == "single" else None
+                dx, acc = x0.grad_buf() if x0 is not None else (_new((N, Cin, H, W), dy), 0)
                 ws_s = _new((nsd,), dy) if nsd else None
+                dx_slot, dx_done = (_out_slot(dy.device, big), _ct.c_int(0)) if x0 is not None else (None, None)
                 _conv_call("jp_conv2d_dgrad", w, "dgrad", sig, nwd,
-                           (dy, w.t, dcat, N, Cin, H, W, Cout, KH, stride, pad, pad_mode, 0), (ws_s, dg_am[0], None, None, dg_am[1]))
+                           (dy, w.t, dx, N, Cin, H, W, Cout, KH, stride, pad, pad_mode, acc),
+                           (ws_s, dg_am[0], dx_slot, _ct.addressof(dx_done) if x0 is not None else None, dg_am[1]))
                 del ws_s
-                c0 = 0
-                for v, u in srcs:
-                    C = v.t.shape[1]
-                    if v.rg:
-                        g, acc = v.grad_buf()
-                        if u:
-                            call("jp_upsample2x_bwd", dcat, g, N, C, H // 2, W // 2, Cin, c0, acc)
-                        else:
-                            call("jp_copy_channels", dcat, g, N, C, H * W, Cin, c0, C, 0, acc)
-                    c0 += C
+                if x0 is None:
+                    _scatter_channels(dx, srcs)
+                elif dx_done.value:       # max |dx| out of the dgrad epilogue (+ border fold): the scale of the next convolution backward
+                    x0.gamax = dx_slot
         out.g = None
 
     _rec(out.rg, bwd)
@@ -676,7 +688,7 @@ def batchnorm_train(x: Var, gamma: Var, beta: Var, running_mean, running_var, re
     y = torch.empty_like(x.t)
     mean = _new((groups, C), x.t)
     invstd = _new((groups, C), x.t)
-    nbw = int(_jplib().fn["jp_bn_ws_doubles"](Ng, C, H * W))
+    nbw = _q("jp_bn_ws_doubles", Ng, C, H * W)
     y_am = _out_slot(y.device, C >= 32)       # max|y| out of the apply kernel: the next convolution's operand scale
     # statistics partials from the producing convolution's epilogue (one group only: a partial never straddles two images, but the
     # kernels deal their pixel tiles out in an order of their own)
@@ -725,7 +737,7 @@ def bn_relu_maxpool_train(x: Var, gamma: Var, beta: Var, running_mean, running_v
     y = _new((N, C, H // 2, W // 2), x.t)
     idx = _new((N, C, H // 2, W // 2), x.t, torch.uint8)
     mean, invstd = _new((groups, C), x.t), _new((groups, C), x.t)
-    nbw = int(_jplib().fn["jp_bn_ws_doubles"](Ng, C, H * W))
+    nbw = _q("jp_bn_ws_doubles", Ng, C, H * W)
     y_am = _out_slot(y.device, C >= 32)       # max of the pooled map out of the kernel: the first residual block's operand scale
     for g in range(groups):
         sl = slice(g * Ng, (g + 1) * Ng)
@@ -739,7 +751,7 @@ def bn_relu_maxpool_train(x: Var, gamma: Var, beta: Var, running_mean, running_v
         if out.g is None:
             return
         dx = torch.empty_like(x.t)
-        nb2 = int(_jplib().fn["jp_bn_relu_pool_bwd_ws_doubles"](Ng, C, H, W))
+        nb2 = _q("jp_bn_relu_pool_bwd_ws_doubles", Ng, C, H, W)
         for g in range(groups):
             sl = slice(g * Ng, (g + 1) * Ng)
             ws2 = _new((nb2,), x.t, torch.float64)
@@ -810,14 +822,13 @@ def maxpool(x: Var, k, s, p, bwd_addend=None) -> Var:
 def upsample2x(x: Var) -> Var:
     N, C, H, W = x.t.shape
     y = _new((N, C, 2 * H, 2 * W), x.t)
-    call("jp_upsample2x_fwd", x.t, y, N, C, H, W, C, 0)
+    _gather_channels([(x, 1)], y)
     out = Var(y, x.rg)
 
     def bwd():
         if out.g is None:
             return
-        g, acc = x.grad_buf()
-        call("jp_upsample2x_bwd", out.g, g, N, C, H, W, C, 0, acc)
+        _scatter_channels(out.g, [(x, 1)])
         out.g = None
 
     _rec(out.rg, bwd)
@@ -828,23 +839,13 @@ def cat_channels(vs) -> Var:
     N, _, H, W = vs[0].t.shape
     Ct = sum(v.t.shape[1] for v in vs)
     y = _new((N, Ct, H, W), vs[0].t)
-    c0 = 0
-    for v in vs:
-        C = v.t.shape[1]
-        call("jp_copy_channels", v.t, y, N, C, H * W, C, 0, Ct, c0, 0)
-        c0 += C
+    _gather_channels([(v, 0) for v in vs], y)
     out = Var(y, any(v.rg for v in vs))
 
     def bwd():
         if out.g is None:
             return
-        c0 = 0
-        for v in vs:
-            C = v.t.shape[1]
-            if v.rg:
-                g, acc = v.grad_buf()
-                call("jp_copy_channels", out.g, g, N, C, H * W, Ct, c0, C, 0, acc)
-            c0 += C
+        _scatter_channels(out.g, [(v, 0) for v in vs])
         out.g = None
 
     _rec(out.rg, bwd)

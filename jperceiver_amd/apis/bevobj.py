@@ -18,7 +18,9 @@ label -1; `count` is the number of kept components even beyond max_objects (`ove
 for split == "argo").  `find` never synchronises and its outputs are pure functions of its inputs; .labels, .count and .table are
 STATIC buffers, valid until the next `find` -- clone what has to live longer.
 
-Not built: tracking or association of objects across frames, oriented boxes (width and length are those of the axis-aligned box in
+Tracking across frames is `BevTracker` (apis/bevtrack.py; in a session objects=dict(track=True)).
+
+Not built: oriented boxes (width and length are those of the axis-aligned box in
 the camera's own BEV frame), splitting vehicles whose cells touch, objects on the world-frame `BevMap`, any drawing of boxes."""
 from __future__ import annotations
 
@@ -36,16 +38,23 @@ OBJECTS_DEFAULTS = dict(max_objects=64, min_cells=4, conn=8, cls=2, off=0.27)
 
 
 def _objects_kw(objects):
-    """None -> None (no objects); True -> {}; a dict -> a copy, its keys checked (cameras, occ and device are the session's)"""
+    """None -> None (no objects); True -> {}; a dict -> a copy, its keys checked (cameras, occ and device are the session's); the
+    entry `track` (None, a bool or a dict of reach, min_overlap: apis/bevtrack.py) is the session's and stays in the copy"""
     if objects is None or objects is False:
         return None
     if not (objects is True or isinstance(objects, dict)):
         raise TypeError("objects must be None, True or a dict of BevObjects keyword arguments (" + ", ".join(OBJECTS_DEFAULTS) + ")")
     kw = {} if objects is True else dict(objects)
-    unknown = sorted(set(kw) - set(OBJECTS_DEFAULTS))
+    unknown = sorted(set(kw) - set(OBJECTS_DEFAULTS) - {"track"})
     if unknown:
-        raise TypeError(f"objects: unknown entries {unknown}; known: {', '.join(OBJECTS_DEFAULTS)}")
-    _check(**{**OBJECTS_DEFAULTS, **kw})
+        raise TypeError(f"objects: unknown entries {unknown}; known: {', '.join(OBJECTS_DEFAULTS)}, track")
+    if "track" in kw:
+        from .bevtrack import _check as _check_track, _track_kw, TRACK_DEFAULTS
+        tk = _track_kw(kw["track"])
+        if tk is not None:                                              # the tracker's table is the objects': its bound on max_objects holds
+            _check_track(kw.get("max_objects", OBJECTS_DEFAULTS["max_objects"]), off=kw.get("off", OBJECTS_DEFAULTS["off"]),
+                         **{**TRACK_DEFAULTS, **tk})
+    _check(**{**OBJECTS_DEFAULTS, **{k: v for k, v in kw.items() if k != "track"}})
     return kw
 
 

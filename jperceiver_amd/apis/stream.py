@@ -48,7 +48,14 @@ of every push ends with one jp_bev_objects call -- the connected components of t
 jp_layout_classes_u8, and in a depth_bev session behind the lift, whose grid it is given (points and height per object).
 `s.objects` is the live `BevObjects`; its `.labels`, `.count` and `.table` are static buffers with the lifetime of the other
 outputs, `s.objects.objects(pose=frame.pose)` is the synchronising read.  `off` defaults from model.opt.split.  The default (None)
-adds nothing to a push."""
+adds nothing to a push.
+
+objects=dict(track=True) (or track=dict(reach=..., min_overlap=...), next to the other entries; apis/bevtrack.py): the pose part of
+every push ends with one jp_bev_tracks call behind jp_stream_traj_push -- it reads the pose that launch has just finished, and the
+labels and table jp_bev_objects left earlier on the same stream -- which gives every object a track id that lasts while the object
+stays in view, its age and its world-frame displacement.  `s.tracks` is the live `BevTracker`; `.tracks_i`, `.kin` and `.stats` are
+static buffers with the lifetime of the other outputs, `s.tracks.tracks(dt)` is the synchronising read.  Without `track` a push is
+what it was."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -78,7 +85,7 @@ class PerceptionStream:
     `BevMap` keyword arguments (`off` defaults from model.opt.split, `occ` is the layouts'); depth_bev: None or a dict of
     `DepthBev` keyword arguments with at least K (`off` defaults from model.opt.split; cameras, occ, src_hw, depth_hw and device
     are the session's); objects: None, True or a dict of `BevObjects` keyword arguments (`off` defaults from model.opt.split;
-    cameras, occ and device are the session's)."""
+    cameras, occ and device are the session's) and, optionally, track: True or a dict of `BevTracker`'s reach and min_overlap."""
 
     def __init__(self, model, src_hw, cameras=1, out_size=None, min_depth=None, max_depth=None, capacity=4096, frozen=True,
                  bev_map=None, depth_bev=None, objects=None):
@@ -93,7 +100,7 @@ class PerceptionStream:
             _ground_kw(depth_bev["ground"])                           # a malformed `ground` is refused before anything else is looked at
         if objects is not None:
             from .bevobj import _objects_kw
-            objects = _objects_kw(objects)                            # ... and so is a malformed `objects`
+            objects = _objects_kw(objects)                            # ... and so is a malformed `objects`, its `track` included
         if model.training:
             raise RuntimeError("PerceptionStream expects an eval-mode model (call .eval(): BatchNorm must use running stats)")
         p = next(model.parameters())
@@ -135,10 +142,15 @@ class PerceptionStream:
             kw.update(cameras=B, occ=int(model.opt.occ_map_size), src_hw=self.src_hw, depth_hw=self.out_size, device=dev)
             self.depth_bev = DepthBev(**kw)
         self.objects = None                                           # the live BevObjects of an objects session
+        self.tracks = None                                            # the live BevTracker of an objects session with `track`
         if objects is not None:
             from .bevobj import BevObjects
+            from .bevtrack import BevTracker, _track_kw
             kw = {"off": 1.9 if getattr(model.opt, "split", None) == "argo" else 0.27, **objects}
+            track = _track_kw(kw.pop("track", None))
             self.objects = BevObjects(B, int(model.opt.occ_map_size), device=dev, **kw)
+            if track is not None:
+                self.tracks = BevTracker(B, self.objects.occ, max_objects=self.objects.max_objects, off=self.objects.off, device=dev, **track)
 
     # ---------------------------------------------------------------------------------------- state
     def reset(self):
@@ -151,6 +163,8 @@ class PerceptionStream:
             self.depth_bev.reset()
         if self.objects is not None:
             self.objects.reset()
+        if self.tracks is not None:
+            self.tracks.reset()
         self._n = 0
 
     def trajectory(self):
@@ -210,6 +224,8 @@ class PerceptionStream:
         aa, tr = m.eval_branch("pose", Var(pair))
         ops.call("jp_pose_fwd", aa.t, tr.t, self._K, self._T, self._P, B, 1)
         ops.call("jp_stream_traj_push", self._T, self._pose, self._traj, self._count, B, self.capacity)
+        if self.tracks is not None:                                   # behind traj_push (the pose) and behind jp_bev_objects (labels, table)
+            self.tracks._update(self.objects.labels, self.objects.count, self.objects.table, self._pose, 16)
         if self._bev_kw is not None:
             if self.bev_map is None:
                 if h != w:

@@ -298,6 +298,56 @@ GROUPS = [
      "B occ occ >= 2^31.  ORDERING in a session: jp_bev_objects behind jp_layout_classes_u8, and with a grid behind jp_depth_bev_lift, "
      "all on one stream.",
      ["jp_bev_objects_ws_bytes", "jp_bev_objects"]),
+    ("BEV object tracks (csrc/bevtrack.hip; apis/bevtrack.py BevTracker, PerceptionStream(objects=dict(track=...))) -- the objects of "
+     "jp_bev_objects associated from one frame to the next by cell overlap under the ego-motion, so that a vehicle keeps one track id "
+     "while it stays in view; no counterpart in the reference.  Every buffer is the caller's (the library keeps no state): the previous "
+     "frame lives in THE STATE, three buffers that every call reads and rolls forward as its last step.  "
+     "jp_bev_tracks: labels (B,occ,occ) int32, count (B) int32 and table (B,max_objects,12) int32 exactly as jp_bev_objects wrote them for "
+     "the current frame; pose: for camera b the current row-major 3x4 or 4x4 float64 camera-to-world transform T at pose + b pose_stride "
+     "doubles (pose_stride 16: the session's pose; 12: trajectory rows).  M = max_objects, n_cur = min(count[b], M): ids >= max_objects "
+     "exist in labels but are not tracked (they vote for nothing, get no row and no track id).  "
+     "THE STATE: prev_labels (B,occ,occ) int32, the label map of the call before; state_i (B, 2 + 2 M) int32 = [n_prev, next_id, then for "
+     "every previous object id its track_id and age]; state_d (B, 12 + 2 M) float64 = [the 12 doubles of rows 0..2 of the previous pose "
+     "P, then for every previous object id its X_w and Z_w].  ZEROED STATE MEANS NO HISTORY (n_prev = 0: every object is a birth, ids "
+     "from 0); n_prev is clamped to 0 .. M when read.  "
+     "OVERLAP, a gather: current cells are gathered from the previous map.  overlap[b][p][c] counts, over every cell (i, j) with "
+     "0 <= labels[b][i][j] = c < M and every (di, dj) in [-reach, reach]^2, the cells (i' + di, j' + dj) inside the map whose "
+     "prev_labels value is p with 0 <= p < n_prev, where (i', j') is the cell of the previous camera's map that the centre of cell "
+     "(i, j) falls into -- in float64 with every operation rounded once (no fma) and in exactly this order, res_f = 40 / occ: "
+     "x = ((j + 0.5) - 0.5 occ) res_f, z = ((occ - 0.5) - i) res_f - off, X = (T[0][0] x + T[0][2] z) + T[0][3], "
+     "Z = (T[2][0] x + T[2][2] z) + T[2][3], dX = X - P[0][3], dZ = Z - P[2][3], det = P[0][0] P[2][2] - P[0][2] P[2][0], "
+     "x' = (P[2][2] dX - P[0][2] dZ) / det, z' = (P[0][0] dZ - P[2][0] dX) / det, u = x' / res_f + 0.5 occ, v = (z' + off) / res_f "
+     "(jp_bev_fuse's inverse and cell rule, without its max_range test); the cell exists iff u >= 0 && u < occ && v >= 0 && v < occ, "
+     "then j' = floor(u), i' = occ - 1 - floor(v); a cell whose centre falls outside the previous map votes for nothing.  Every range "
+     "test is false for NaN and nothing is converted to an integer before the test that bounds it has passed.  A previous pose with "
+     "!(|det| >= 1e-6) gives no votes, and so does a current pose one of whose six elements read is not finite: every object is then a "
+     "birth.  overlap lives in ws (jp_bev_tracks_ws_bytes(B, occ, max_objects) = 4 B M M bytes); the call zeroes it itself.  "
+     "ASSIGNMENT, greedy: repeatedly the pair (p, c), p < n_prev, c < n_cur, of largest overlap among the unused rows and columns is "
+     "matched; TIE-BREAK: the smaller p, then the smaller c; it stops when the best overlap is < min_overlap.  The kernel takes the "
+     "maximum of a packed 64-bit key per round and gives exactly the matches of that sequential loop.  "
+     "TRACK UPDATE: a matched object inherits the track id of p and age = age of p + 1; the unmatched current objects are BIRTHS: in "
+     "ascending object id each takes track = next_id++ (a counter per camera, in the state) and age = 1; the unmatched previous objects "
+     "end: a track ends in the first frame it is not matched (no coasting).  "
+     "OUTPUTS: tracks (B,M,4) int32, row c = [track_id, age, prev_obj (-1 for a birth), overlap (0 for a birth)], rows >= n_cur are "
+     "[-1, 0, -1, 0]; kin (B,M,4) float64, row c = [X_w, Z_w, dX_w, dZ_w]: with x = ((sum_c / cells + 0.5) - 0.5 occ) res_f, "
+     "z = ((occ - 0.5) - sum_r / cells) res_f - off from the object's table row (the centroid of its cell centres), "
+     "X_w = (T[0][0] x + T[0][2] z) + T[0][3], Z_w = (T[2][0] x + T[2][2] z) + T[2][3], and dX_w = X_w - the stored X_w of p, "
+     "dZ_w likewise, for a match, 0 for a birth; rows >= n_cur are 0; stats (B,4) int32 = [n_cur, matched, born, ended].  "
+     "Every output is fully overwritten: tracks, kin, stats and ws need not be initialised.  "
+     "STATE ROLL, the last step of the same call: prev_labels = labels, P = rows 0..2 of T, n_prev = n_cur, next_id += born, and per "
+     "current object its track_id, age, X_w and Z_w (rows >= n_cur zero): the host swaps no pointers, every launch has the same "
+     "arguments from frame to frame.  One call enqueues four launches on `stream` -- zero the matrix; the vote, one thread per current "
+     "cell, its votes folded in wave-local runs and (max_objects <= 64) an LDS tile of the matrix before they reach global memory "
+     "(JP_BEV_TRACKS_VOTE=0 / 1 / 2, read at every call, selects per-vote atomics / the runs / the tile: integer sums, the same matrix); "
+     "the assignment, update and roll of the small state, one workgroup per camera; the copy of the label map -- a phase that needs a "
+     "global order is a launch of its own: no workgroup waits on another.  The votes are integer atomicAdd and the float64 values a "
+     "fixed sequence of single-rounded operations: two runs give the same bytes.  Refused before any launch (-1 and a message): a NULL "
+     "pointer (all but stream are required); non-positive B, occ or max_objects; occ > 1024; max_objects > 256 (the overlap matrix and "
+     "the rounds of the assignment grow with its square); reach outside 0 .. 3; min_overlap < 1; pose_stride not 12 or 16; off not "
+     "finite; B occ occ >= 2^31; B max_objects max_objects >= 2^31.  jp_bev_tracks_ws_bytes returns 0 for a non-positive argument.  "
+     "ORDERING in a session: jp_bev_tracks behind jp_bev_objects (it reads labels, count and table) and behind jp_stream_traj_push (the "
+     "pose it reads is finished by that launch), all on one stream.",
+     ["jp_bev_tracks_ws_bytes", "jp_bev_tracks"]),
     ("KITTI odometry evaluation (csrc/odometry.hip; core/evaluation.py::eval_odometry, apis/inference.py) — the pose chaining of "
      "scripts/draw_odometry.py:62-76 and the numpy toolkit behind the paper's t_err / r_err (mono/tools/kitti_evaluation_toolkit.py:"
      "109-201, mono/tools/geometry.py:20-67, scripts/plot_kitti.py:15-97,223-243).  All arithmetic is double, no atomics: every sum "

@@ -53,7 +53,7 @@ def _objects_kw(objects):
         tk = _track_kw(kw["track"])
         if tk is not None:                                              # the tracker's table is the objects': its bound on max_objects holds
             _check_track(kw.get("max_objects", OBJECTS_DEFAULTS["max_objects"]), off=kw.get("off", OBJECTS_DEFAULTS["off"]),
-                         **{**TRACK_DEFAULTS, **tk})
+                         **{**TRACK_DEFAULTS, **{k: v for k, v in tk.items() if k != "filter"}})
     _check(**{**OBJECTS_DEFAULTS, **{k: v for k, v in kw.items() if k != "track"}})
     return kw
 

@@ -20,7 +20,10 @@ inputs and the state.  .tracks_i (cameras, max_objects, 4) int32 [track_id, age,
 float64 [X_w, Z_w, dX_w, dZ_w] and .stats (cameras, 4) int32 [n_cur, matched, born, ended] are STATIC buffers, valid until the next
 `update` -- clone what has to live longer.
 
-Not built: coasting a track through a missed frame, any motion model or filter, split and merge bookkeeping beyond what greedy
+Coasting a track through a missed frame, the repair of an id switch and a filter on the motion are a stage of their own behind this
+one: `BevTrackFilter` (apis/bevfilter.py; in a session objects=dict(track=dict(filter=True))).
+
+Not built: split and merge bookkeeping beyond what greedy
 overlap gives (of two objects that merge, one track goes on and the other ends; of one that splits, one part keeps the id and the
 other is born), association across cameras, tracks on the world-frame `BevMap`, any drawing."""
 from __future__ import annotations
@@ -47,16 +50,20 @@ def _check(max_objects, reach, min_overlap, off):
 
 
 def _track_kw(track):
-    """None / False -> None (no tracking); True -> {}; a dict -> a copy, its keys (reach, min_overlap) and values checked"""
+    """None / False -> None (no tracking); True -> {}; a dict -> a copy, its keys (reach, min_overlap) and values checked; the entry
+    `filter` (None, a bool or a dict of `BevTrackFilter` keyword arguments: apis/bevfilter.py) is the session's and stays in the copy"""
     if track is None or track is False:
         return None
     if not (track is True or isinstance(track, dict)):
         raise TypeError("track must be None, a bool or a dict of BevTracker keyword arguments (" + ", ".join(TRACK_DEFAULTS) + ")")
     kw = {} if track is True else dict(track)
-    unknown = sorted(set(kw) - set(TRACK_DEFAULTS))
+    unknown = sorted(set(kw) - set(TRACK_DEFAULTS) - {"filter"})
     if unknown:
-        raise TypeError(f"track: unknown entries {unknown}; known: {', '.join(TRACK_DEFAULTS)}")
-    _check(1, off=0.0, **{**TRACK_DEFAULTS, **kw})
+        raise TypeError(f"track: unknown entries {unknown}; known: {', '.join(TRACK_DEFAULTS)}, filter")
+    if "filter" in kw:
+        from .bevfilter import _filter_kw
+        _filter_kw(kw["filter"])
+    _check(1, off=0.0, **{**TRACK_DEFAULTS, **{k: v for k, v in kw.items() if k != "filter"}})
     return kw
 
 

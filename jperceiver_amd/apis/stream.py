@@ -55,7 +55,13 @@ every push ends with one jp_bev_tracks call behind jp_stream_traj_push -- it rea
 labels and table jp_bev_objects left earlier on the same stream -- which gives every object a track id that lasts while the object
 stays in view, its age and its world-frame displacement.  `s.tracks` is the live `BevTracker`; `.tracks_i`, `.kin` and `.stats` are
 static buffers with the lifetime of the other outputs, `s.tracks.tracks(dt)` is the synchronising read.  Without `track` a push is
-what it was."""
+what it was.
+
+objects=dict(track=dict(filter=True)) (or filter=dict(max_tracks, max_coast, min_hits, gate, meas_sigma, vel_sigma0, accel_sigma), next
+to reach and min_overlap; apis/bevfilter.py): every push then ends its pose part with one jp_bev_track_filter call directly behind
+jp_bev_tracks -- persistent ids that coast through missed frames, a life cycle and a filtered world-frame velocity per track.
+`s.track_filter` is the live `BevTrackFilter` (None otherwise); `.slots_i`, `.slots_d`, `.obj_slot` and `.fstats` are static buffers,
+`s.track_filter.tracks(dt)` is the synchronising read; `reset()` resets it with the tracker.  Without `filter` a push is what it was."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -85,7 +91,8 @@ class PerceptionStream:
     `BevMap` keyword arguments (`off` defaults from model.opt.split, `occ` is the layouts'); depth_bev: None or a dict of
     `DepthBev` keyword arguments with at least K (`off` defaults from model.opt.split; cameras, occ, src_hw, depth_hw and device
     are the session's); objects: None, True or a dict of `BevObjects` keyword arguments (`off` defaults from model.opt.split;
-    cameras, occ and device are the session's) and, optionally, track: True or a dict of `BevTracker`'s reach and min_overlap."""
+    cameras, occ and device are the session's) and, optionally, track: True or a dict of `BevTracker`'s reach and min_overlap and, optionally,
+    filter: True or a dict of `BevTrackFilter` keyword arguments."""
 
     def __init__(self, model, src_hw, cameras=1, out_size=None, min_depth=None, max_depth=None, capacity=4096, frozen=True,
                  bev_map=None, depth_bev=None, objects=None):
@@ -143,6 +150,7 @@ class PerceptionStream:
             self.depth_bev = DepthBev(**kw)
         self.objects = None                                           # the live BevObjects of an objects session
         self.tracks = None                                            # the live BevTracker of an objects session with `track`
+        self.track_filter = None                                      # the live BevTrackFilter of a `track` session with `filter`
         if objects is not None:
             from .bevobj import BevObjects
             from .bevtrack import BevTracker, _track_kw
@@ -150,7 +158,11 @@ class PerceptionStream:
             track = _track_kw(kw.pop("track", None))
             self.objects = BevObjects(B, int(model.opt.occ_map_size), device=dev, **kw)
             if track is not None:
+                from .bevfilter import BevTrackFilter, _filter_kw
+                flt = _filter_kw(track.pop("filter", None), self.objects.max_objects)
                 self.tracks = BevTracker(B, self.objects.occ, max_objects=self.objects.max_objects, off=self.objects.off, device=dev, **track)
+                if flt is not None:
+                    self.track_filter = BevTrackFilter(B, max_objects=self.objects.max_objects, occ=self.objects.occ, device=dev, **flt)
 
     # ---------------------------------------------------------------------------------------- state
     def reset(self):
@@ -165,6 +177,8 @@ class PerceptionStream:
             self.objects.reset()
         if self.tracks is not None:
             self.tracks.reset()
+        if self.track_filter is not None:                             # with the tracker: its ids start from 0 again
+            self.track_filter.reset()
         self._n = 0
 
     def trajectory(self):
@@ -226,6 +240,8 @@ class PerceptionStream:
         ops.call("jp_stream_traj_push", self._T, self._pose, self._traj, self._count, B, self.capacity)
         if self.tracks is not None:                                   # behind traj_push (the pose) and behind jp_bev_objects (labels, table)
             self.tracks._update(self.objects.labels, self.objects.count, self.objects.table, self._pose, 16)
+            if self.track_filter is not None:                         # directly behind jp_bev_tracks: it reads tracks_i, kin and stats
+                self.track_filter._update(self.tracks.tracks_i, self.tracks.kin, self.tracks.stats)
         if self._bev_kw is not None:
             if self.bev_map is None:
                 if h != w:

@@ -348,6 +348,58 @@ GROUPS = [
      "ORDERING in a session: jp_bev_tracks behind jp_bev_objects (it reads labels, count and table) and behind jp_stream_traj_push (the "
      "pose it reads is finished by that launch), all on one stream.",
      ["jp_bev_tracks_ws_bytes", "jp_bev_tracks"]),
+    ("Filtered BEV tracks (csrc/bevfilter.hip; apis/bevfilter.py BevTrackFilter, PerceptionStream(objects=dict(track=dict(filter=...)))) "
+     "-- a stage behind jp_bev_tracks that coasts its tracks through missed frames, repairs its id switches and filters their motion: "
+     "a persistent id (fid), a life cycle tentative -> confirmed -> coasting -> ended, and per world axis a constant-velocity Kalman "
+     "filter; no counterpart in the reference.  Every buffer is the caller's (the library keeps no state): THE STATE is also the output, "
+     "every call reads it and rolls it forward.  "
+     "jp_bev_track_filter reads what jp_bev_tracks wrote for the current frame and never a label map: tracks (B,M,4) int32, kin (B,M,4) "
+     "float64, stats (B,4) int32; M = max_objects, S = max_tracks.  "
+     "THE STATE, three row layouts: slots_i (B,S,8) int32, row s = [fid, status, src_track, age, hits, misses, obj, 0], status 0 free, "
+     "1 tentative, 2 confirmed, 3 coasting, src_track the jp_bev_tracks id the slot follows, obj the current object id or -1 while "
+     "coasting; slots_d (B,S,10) float64, row s = [X, Z, vX, vZ, aX, bX, cX, aZ, bZ, cZ], metres and metres per frame, the two axes "
+     "decoupled, each with the symmetric covariance [[a, b], [b, c]] of [position, velocity]; head (B,2) int32 = [next_fid, calls].  "
+     "ZEROED STATE MEANS NO HISTORY (every slot free, fids from 0).  A slot is LIVE iff its status is 1, 2 or 3; the row of a slot that "
+     "is not live when the call ends is written as zeros whatever it held.  "
+     "OUTPUTS, fully overwritten (they need not be initialised): obj_slot (B,M) int32, the slot of current object c or -1; fstats (B,8) "
+     "int32 = [live, confirmed, coasting, continued, reacquired, born, ended, dropped].  "
+     "With r = meas_sigma meas_sigma, q = accel_sigma accel_sigma, c0 = vel_sigma0 vel_sigma0 and gate gate -- each squared once inside "
+     "the call, one rounded multiply -- a call does, per camera, exactly this sequential definition.  "
+     "0. OBJECTS: n = min(max(stats[b][0], 0), M); object c < n has t_c = tracks[b][c][0] and the measurement z_c = (kin[b][c][0], "
+     "kin[b][c][1]); it is VALID iff both are finite, an invalid object is ignored everywhere.  No value read from device memory is used "
+     "as an index before it is range-checked; track ids are only compared.  "
+     "1. PREDICT every live slot, per axis: p' = p + v, v' = v, a' = ((a + (b + b)) + c) + q/4, b' = (b + c) + q/2, c' = c + q.  "
+     "2. CONTINUE: valid object c is bound to slot s iff s is live with misses == 0 and src_track == t_c; the ids of jp_bev_tracks are "
+     "unique within a frame and never reused, so there is at most one such slot (for any other state: a slot picks the smallest such c, "
+     "and c is bound to the smallest slot that picked it).  "
+     "3. RE-ACQUIRE: the candidate slots are the live slots not bound in step 2 (the coasting ones, and those whose tracker track ended "
+     "in this very frame: the id-switch repair), the candidate objects the valid unbound ones; dx = z_c.X - X', dz = z_c.Z - Z' from the "
+     "PREDICTED position, d2 = dx dx + dz dz (two rounded products, one rounded sum); a pair qualifies iff d2 <= gate gate (false for "
+     "NaN); greedy: repeatedly the qualifying pair of smallest d2 among the unused slots and objects is matched, TIE-BREAK: the smaller "
+     "slot index, then the smaller object id, until no pair qualifies; a match rebinds src_track = t_c.  "
+     "4. BIRTHS: the remaining valid unbound objects, in ascending object id, take the slots that were free at entry of the call, in "
+     "ascending slot index (a slot freed in step 6 of a call is taken in the next call at the earliest); each takes fid = next_fid++ in "
+     "that order; objects that find no slot are counted in dropped and take no fid.  Initial state: position = measurement, velocity 0, "
+     "covariance [[r, 0], [0, c0]] per axis, src_track = t_c, age = hits = 1, misses = 0.  "
+     "5. UPDATE the bound and the re-acquired slots from the predicted state, per axis with the measurement z: y = z - p', S = a' + r, "
+     "K1 = a' / S, K2 = b' / S, p = p' + K1 y, v = v' + K2 y, a = a' - K1 a', b = b' - K1 b', c = c' - K2 b'; age++, hits++, "
+     "misses = 0, obj = c.  "
+     "6. MISS, the live slots still unbound: a tentative slot, or one with misses + 1 > max_coast, is freed (its whole row zeroed, "
+     "counted in ended); any other keeps the predicted state with misses++, age++, status = 3, obj = -1.  "
+     "7. STATUS of every slot that has a measurement (steps 4 and 5): 2 if hits >= min_hits, else 1.  "
+     "Then fstats: live, confirmed and coasting count the slots by status as the call leaves them, continued / reacquired / born / ended / "
+     "dropped the decisions of steps 2, 3, 4, 6 and 4; head = [next_fid, calls + 1].  "
+     "ARITHMETIC: float64, every operation rounded once (no fma), in the order written; the result is a pure function of the arguments "
+     "and the state: two runs give the same bytes.  One call is ONE launch with fixed arguments on `stream`, grid (B): one workgroup per "
+     "camera, one thread per slot and per object, no atomics, no workspace; no workgroup waits on another.  The S x M distances are never "
+     "stored: a slot keeps its nearest free object and rescans when another slot takes it, a round is one minimum over the bit pattern "
+     "of the non-negative d2.  Refused before any launch (-1 and a message): a NULL pointer (all but stream are required); non-positive "
+     "B, max_objects or max_tracks; max_objects > 256; max_tracks > 256; max_coast < 0; min_hits < 1; gate, vel_sigma0 or accel_sigma "
+     "not finite or negative; meas_sigma not finite or not greater than zero; B max_tracks 10 >= 2^31; B max_objects 4 >= 2^31.  "
+     "ORDERING in a session: jp_bev_track_filter behind jp_bev_tracks (it reads tracks, kin and stats), on one stream.  RESET BOTH: "
+     "resetting the tracker without resetting the filter lets stale src_track values match new tracks (the tracker numbers its tracks "
+     "from 0 again).",
+     ["jp_bev_track_filter"]),
     ("KITTI odometry evaluation (csrc/odometry.hip; core/evaluation.py::eval_odometry, apis/inference.py) — the pose chaining of "
      "scripts/draw_odometry.py:62-76 and the numpy toolkit behind the paper's t_err / r_err (mono/tools/kitti_evaluation_toolkit.py:"
      "109-201, mono/tools/geometry.py:20-67, scripts/plot_kitti.py:15-97,223-243).  All arithmetic is double, no atomics: every sum "

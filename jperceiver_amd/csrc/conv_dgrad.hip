@@ -642,56 +642,311 @@ const char* p9s2d_tag() { return __PRETTY_FUNCTION__; }
 
 }  // namespace
 
+// ---- geometry of one input-gradient call, read by every route predicate, plan and launcher (the scratch queries: no pad mode, every
+// scratch given).  For a per-source call it describes the whole bank (Cin = all sources' channels).
+struct KSlices {
+    int kps, n;     // K per slice (a multiple of KC) and the slices that gives
+};
+static inline KSlices k_slices(int Kp, int sp) {
+    const int kps = jp_cdiv(jp_cdiv(Kp, sp), KC) * KC;
+    return KSlices{kps, jp_cdiv(Kp, kps)};
+}
+struct DgradGeom {
+    int N, Cin, H, W, Cout, KH, stride, pad, pad_mode;
+    bool has_ws, has_split;     // the pack scratch `ws` / the split scratch `split_ws` were given
+    int OH, OW, Cp, Kp;
+    long npix;
+    int KK() const { return KH * KH; }
+    bool reflect() const { return pad_mode == JP_PAD_REFLECT; }
+    bool s1_3x3() const { return KH == 3 && stride == 1 && pad == 1; }
+    bool halves() const { return H % 2 == 0 && W % 2 == 0 && 2 * OH == H && 2 * OW == W; }      // an even map onto exactly its half
+    // 3x3 stride 2 pad 1 on an even map; s2_parity: and the pixels of one parity class fill whole 256-pixel tiles (the generic
+    // parity-class form; maps it does not take, e.g. the 8 x 8 maps of the 256^2 test shapes, run the plain loader)
+    bool s2_form() const { return KH == 3 && stride == 2 && pad == 1 && !reflect() && halves(); }
+    long Nc() const { return (long)N * (H / 2) * (W / 2); }
+    bool s2_parity() const { return s2_form() && Nc() % 256 == 0; }
+    // rows of a short row tail, 0 = none: 513 = 4*128 + 1 input channels of the iconv layers run the tail as its own 64-row launch
+    // instead of a fifth, almost empty 128-row tile column
+    int tail() const { return (Cin > 128 && Cin % 128 <= 16) ? Cin % 128 : 0; }
+    int small_grid() const { return small_grid_splits(Cin, npix, Kp); }      // K slices of a tile grid that cannot fill the chip
+    int ring(int h, int w) const { return N * (2 * w + 2 * h); }             // border-adjacent (edge) pixels of the N (h, w) maps
+};
+static DgradGeom dgrad_geom(int N, int Cin, int H, int W, int Cout, int KH, int stride, int pad, int pad_mode, bool has_ws,
+                            bool has_split) {
+    DgradGeom g{N, Cin, H, W, Cout, KH, stride, pad, pad_mode, has_ws, has_split};
+    g.OH = stride > 0 ? (H + 2 * pad - KH) / stride + 1 : 0;
+    g.OW = stride > 0 ? (W + 2 * pad - KH) / stride + 1 : 0;
+    g.Cp = pad32(Cout);
+    g.Kp = KH * KH * g.Cp;
+    g.npix = (long)N * H * W;
+    return g;
+}
+// the row-tile kernel takes M rows of a 3x3 stride-1 bank: whole 256- (up to 64 rows) or 128-pixel tiles per image row
+static inline bool row_tile_ok(const DgradGeom& g, int M) {
+    return g.s1_3x3() && g.Cout >= 32 && g.W % (M <= 64 ? 256 : 128) == 0 && g.npix > 64;
+}
+
+// ---- split plan of the ring passes: the reflection border pass of a full-resolution bank (C rows over the Nb border-adjacent pixels)
+// and the edge pass of an upsampled segment (over the Nb boundary pixels of the half-resolution map).  Their cost is the scattered
+// read-modify-write of the epilogue, not the K loop (border_splits), so K is split only for a few dozen tiles.  Given scratch, the
+// slices are stored (coalesced along the ring) and ONE small pass folds them into dx in a fixed order; without it they meet in the
+// epilogue's atomics.  The two passes wish for slices differently, as found: the border pass asks for up to `cap` slices of at least
+// 9 chunks while that gives fewer than `floor` tiles, whatever the epilogue would do; the edge pass (16 slots x Cout: a long K loop
+// of branchy gathers) splits for the epilogue up to 4 ways below `floor` tiles and sends at most `cap` of those slices to scratch.
+struct RingPolicy {
+    int cap, floor;
+    bool from_epilogue;
+};
+constexpr RingPolicy BORDER_RING{4, 512, false}, EDGE_RING{8, 256, true};
+struct RingPlan {
+    KSlices sl;
+    bool scratch;       // through split_ws and the fold kernel; else the read-modify-write epilogue (atomic where sl.n > 1)
+};
+static RingPlan ring_plan(int C, int Nb, int Kp, bool scratch_given, const RingPolicy& pol) {
+    const long btiles = (long)jp_cdiv(C, C <= 64 ? 64 : 128) * jp_cdiv(Nb, C <= 64 ? 256 : 128);
+    const int chunks = Kp / KC;
+    int esp = border_splits(btiles, chunks), wish;
+    if (pol.from_epilogue) {
+        esp = (int)std::max<long>(esp, std::min<long>(4, jp_cdiv(pol.floor, btiles)));
+        wish = std::min(k_slices(Kp, esp).n, pol.cap);
+    } else {
+        wish = (int)std::max<long>(1, std::min<long>(std::min<long>(pol.cap, chunks / 9), jp_cdiv(pol.floor, btiles)));
+    }
+    const bool scratch = scratch_given && wish > 1;
+    return RingPlan{k_slices(Kp, scratch ? wish : esp), scratch};
+}
+static inline long ring_floats(const RingPlan& p, int C, int Nb) { return p.scratch ? (long)p.sl.n * C * Nb : 0; }
+static inline bool border_via_ws() {
+    static const bool on = [] { const char* e_ = getenv("JP_BORDER_WS"); return !(e_ && e_[0] == '0'); }();
+    return on;
+}
+static inline RingPlan border_plan(const DgradGeom& g, int C) {
+    return ring_plan(C, g.ring(g.H, g.W), g.Kp, border_via_ws() && g.has_split, BORDER_RING);
+}
+static inline RingPlan edge_plan(const DgradGeom& g, int C) { return ring_plan(C, g.ring(g.H / 2, g.W / 2), 16 * g.Cp, g.has_split, EDGE_RING); }
+
+// ---- which kernel runs: dgrad_route alone decides for jp_conv2d_dgrad, precedence is the order of its body = the order of this table.
+// Every kind between DG_C16 and DG_CHANNEL_MAJOR needs the pack scratch `ws` and Cout >= 16.  s2 form = 3x3 stride 2 pad 1 on an even
+// map; sp = small_grid_splits of the tile grid; tail = the 1 channel of 513 (DgradGeom::tail), run by a launch of its own on the same
+// pack (DgradBT x DgradEpi) behind the main pass over the other Mm rows.  A reflection layer (3x3 stride 1) is followed by the border
+// pass (ring_plan: through scratch and border_add_kernel, or its read-modify-write epilogue) behind every kind from DG_P9SM down to
+// DG_TAP.  Packs: T = tap-major (pack_weights), F = fragment-order behind it (pack_p9), built when ws_state == 0.
+//   kind              predicate                                                          kernel                                 packs  fold
+//   DG_C16            jp_c16_ok (16 -> 16, 3x3)                                          conv_c16.hip                           -      -
+//   DG_P9S2D          s2 form, JP_P9S / JP_P9S2 / JP_P9S2D on, Cin >= 32, Cout % 16 == 0, jp_igemm_p9s2d_kernel<1, 4 | 2, 2>     F      -
+//                     OW % 32 == 0, OH % (8 | 4) == 0, dY < 2 GiB, >= 192 workgroups
+//   DG_P1S2           1x1 stride 2 pad 0 on an even map, p1s2_ok                         launch_p9s<DgradS2PointEpi, 1>         F      -
+//   DG_S2_PARITY      s2 form, N * H/2 * W/2 % 256 == 0                                  igemm PackAS2 x DgradS2B               T      -
+//   DG_P9SM           no tail, p9sm_wanted, one split or split_ws given                  jp_p9sm_launch                         T F    slice_reduce_nchw
+//   DG_SPLIT_SCRATCH  sp > 1, split_ws given                                             igemm PackA x DgradBT -> WgradEpiWS    T      slice_reduce_nchw
+//   DG_SPLIT_ATOMIC   sp > 1                                                             memset, the same -> AtomicEpi          T      atomics
+//   DG_P1             stride 1, 1x1 pad 0, no tail, p9_ok(Cin, .., 1)                    launch_p1                              T F    -
+//   DG_P9 (+ tail)    3x3 stride 1 pad 1, tail 0 or Mm > 64, p9_ok(Mm, ..)               launch_p9<false, true>                 (T) F  -
+//                                                                                        (T: only for a tail or a border pass)
+//   DG_ROW_TILE (+ tail)  row_tile_ok(Mm): 3x3 stride 1 pad 1, Cout >= 32,                   launch_r3<1, 4 | 2, 2>                 T      -
+//                     W % (256 | 128) == 0, > 64 pixels
+//   DG_TAP (+ tail)   the rest, either stride                                            igemm PackA x DgradBT<KH, S1>          T      -
+//   DG_CHANNEL_MAJOR  no ws, or Cout < 16                                                igemm DgradA x DgradB                  -      -
+// and for the sources of a per-source call (dgrad_src3_route: unless the whole call is the up-head, Src3Route::up_head, one kind per
+// segment; a source whose gradient is not wanted is DG_NONE).  Full-resolution segments, each followed by the border pass over its rows:
+//   DG_SMALL          C <= 4 (the disparity channel)                                     conv_small.hip on flipped taps
+//   DG_P9             Cin > 64, C > 64 at a multiple of the bank's M tile, p9_ok(C, ..)  launch_p9 on the bank's F pack, from tile coff / bmt
+//   DG_ROW_TILE       row_tile_ok(C)                                                     launch_r3
+//   DG_TAP            the rest                                                           igemm PackA x DgradBT<3, true>
+// the upsampled segment, followed by the edge pass (ring_plan: through scratch and edge_add_kernel, or the atomic epilogue):
+//   DG_P9SD           JP_P9SD on, h2 % 4 == 0, w2 % 32 == 0, Cout % 16 == 0, dY < 2 GiB, >= 192 workgroups  jp_igemm_p9sd_kernel
+//   DG_UP_TAP         the rest                                                           igemm PackA x DgradUPB
+enum DgradKind { DG_C16, DG_P9S2D, DG_P1S2, DG_S2_PARITY, DG_P9SM, DG_SPLIT_SCRATCH, DG_SPLIT_ATOMIC, DG_P1, DG_P9, DG_ROW_TILE, DG_TAP,
+                 DG_CHANNEL_MAJOR, DG_NONE, DG_SMALL, DG_P9SD, DG_UP_TAP };
+struct DgradRoute {
+    DgradKind kind;
+    int Mm, tail;           // rows of the main pass and of the tail launch behind it
+    KSlices sl;             // DG_SPLIT_*: the small-grid slices
+    JpP9smPlan sm;          // DG_P9SM
+    bool pack_tap;          // the route reads the tap-major pack (as found, also built for DG_P9SM, which reads it in the border pass only, and DG_P1)
+    int frag_bmt, frag_khw; // ... the fragment-order pack with this M tile and tap count (frag_bmt == 0: none)
+    bool border;            // a reflection border pass follows, planned by `ring`
+    RingPlan ring;
+    long split_use;         // floats of split_ws the route writes (jp_conv2d_dgrad_split_floats answers at least this)
+};
+static DgradRoute dgrad_route(const DgradGeom& g) {
+    const int N = g.N, Cin = g.Cin, H = g.H, W = g.W, Cout = g.Cout, OH = g.OH, OW = g.OW;
+    DgradRoute r{};
+    r.Mm = Cin;
+    auto is = [&](DgradKind k, bool tap, int frag_bmt, int frag_khw, long use) {
+        r.kind = k;
+        r.pack_tap = tap;
+        r.frag_bmt = frag_bmt;
+        r.frag_khw = frag_khw;
+        r.border = g.reflect() && k >= DG_P9SM && k <= DG_TAP;
+        if (r.border) r.ring = border_plan(g, Cin);
+        r.split_use = std::max(use, r.border ? ring_floats(r.ring, Cin, g.ring(H, W)) : 0);
+        return r;
+    };
+    if (jp_c16_ok(Cin, Cout, g.KH, g.stride, g.pad, g.pad_mode, H, W)) return is(DG_C16, false, 0, 0, 0);
+    if (!(g.has_ws && Cout >= 16)) return is(DG_CHANNEL_MAJOR, false, 0, 0, 0);
+    // 3x3 stride-2 layers: class-uniform split-bf16 kernel on the half-resolution grid (its own fragment-order pack only)
+    const int tr2 = Cin <= 64 ? 8 : 4, bm2 = Cin <= 64 ? 64 : 128;
+    if (g.s2_form() && p9s_enabled() && p9s2_enabled() && JP_ENV_ON("JP_P9S2D") && Cin >= 32 && Cout % 16 == 0 && OW % 32 == 0 &&
+        OH % tr2 == 0 && (long)N * Cout * OH * OW * 4 < (1L << 31) && (long)jp_cdiv(Cin, bm2) * N * (OH / tr2) * (OW / 32) * 4 >= 192)
+        return is(DG_P9S2D, false, bm2, 9, 0);
+    // 1x1 stride 2: the stride-1 1x1 kernel over the half-resolution dY, scattering epilogue
+    if (g.KH == 1 && g.stride == 2 && g.pad == 0 && g.halves() && p1s2_ok(Cin, Cout, N, OH, OW))
+        return is(DG_P1S2, false, p9_bmt(Cin, 1, p9_ptiles(N, OH, OW)), 1, 0);
+    if (g.s2_parity()) return is(DG_S2_PARITY, true, 0, 0, 0);       // 4 tap slots instead of 9 taps per input pixel
+    // small maps: main pass on the split-bf16 patch kernel (taps mirrored, zero fill), then the reflection fold as usual
+    const int tail = g.tail();
+    if (!tail && p9sm_wanted(Cin, Cout, N, H, W, g.KH, g.stride, g.pad, &r.sm) && (r.sm.splits == 1 || g.has_split))
+        return is(DG_P9SM, true, r.sm.bmt, g.KK(), r.sm.part_floats);
+    // small grids: K slices to scratch and a fixed-order reduction (no memset, no atomics), or into a zeroed dx by atomics
+    const int sp = g.small_grid();
+    if (sp > 1) {
+        r.sl = k_slices(g.Kp, sp);
+        return g.has_split ? is(DG_SPLIT_SCRATCH, true, 0, 0, (long)r.sl.n * Cin * g.npix) : is(DG_SPLIT_ATOMIC, true, 0, 0, 0);
+    }
+    // the main launch covers the first Mm rows; a row tail is finished by its own launch on the same pack
+    r.tail = tail;
+    r.Mm = Cin - tail;
+    if (g.stride == 1) {
+        if (g.KH == 1 && g.pad == 0 && tail == 0 && p9_ok(Cin, Cout, N, H, W, 1)) return is(DG_P1, true, p9_bmt(Cin, 1, p9_ptiles(N, H, W)), 1, 0);
+        // P9 patch kernel on dY (taps mirrored, zero fill; the reflection fold stays with the border pass).  With a short row tail
+        // (513 = 4*128 + 1) the kernel runs the full 128-row tiles of the whole bank's pack.  A zero-padded layer it covers completely
+        // never reads the tap-major pack: that is neither built nor replayed for it.
+        if (g.s1_3x3() && (tail == 0 || r.Mm > 64) && p9_ok(r.Mm, Cout, N, H, W))
+            return is(DG_P9, tail || g.reflect(), p9_bmt(Cin, 9, p9_ptiles(N, H, W)), 9, 0);
+        if (row_tile_ok(g, r.Mm)) return is(DG_ROW_TILE, true, 0, 0, 0);
+    }
+    return is(DG_TAP, true, 0, 0, 0);
+}
+
+// Scratch queries.  A query has no pad mode and cannot know whether the scratch will come: it answers for a call that gets it, and
+// returns the maximum over the candidates its arguments leave open -- the border pass at its cap for every 3x3 stride-1 pad-1 layer,
+// the small-map plan whether or not the launch side prefers another kernel, the small-grid slices.  ops.py allocates by these numbers.
 // floats of jp_conv2d_dgrad's optional `split_ws` (as jp_conv2d_fwd_split_floats, conv_fwd.hip, for the forward)
 extern "C" long jp_conv2d_dgrad_split_floats(int N, int Cin, int H, int W, int Cout, int KH, int stride, int pad) {
     if (Cout < 16) return 0;
-    const long npix = (long)N * H * W;
-    const int Kp = KH * KH * pad32(Cout);
-    // 3x3 stride 2: the parity-class forms need no split; maps they do not take (N * H/2 * W/2 not a multiple of 256: the 8 x 8 maps of
-    // the 256^2 test shapes) run the generic loader, whose small-grid K slices must not meet in atomics (round 6: that was the first
-    // run-dependent sum of the backward at those shapes, tools/debug/first_divergence.py)
-    if (KH == 3 && stride == 2 && pad == 1 && H % 2 == 0 && W % 2 == 0 && ((long)N * (H / 2) * (W / 2)) % 256 == 0) return 0;
-    // reflection layers (the pad mode is not an argument here: every 3x3 stride-1 pad-1 layer gets it): <= 4 slices of the
-    // border pass, part[slice][Cin][N * (2H + 2W)]
-    long border = (KH == 3 && stride == 1 && pad == 1) ? 4L * Cin * N * (2L * H + 2L * W) : 0;
+    const DgradGeom g = dgrad_geom(N, Cin, H, W, Cout, KH, stride, pad, JP_PAD_ZERO, true, true);
+    // the parity-class forms need no split; the stride-2 maps they do not take run the generic loader, whose small-grid K slices
+    // must not meet in atomics (that was the first run-dependent sum of the backward at those shapes, tools/debug/first_divergence.py)
+    if (g.s2_parity()) return 0;
+    long need = g.s1_3x3() ? (long)BORDER_RING.cap * Cin * N * (2L * H + 2L * W) : 0;
     JpP9smPlan sm;
-    if (p9sm_wanted(Cin, Cout, N, H, W, KH, stride, pad, &sm)) border = std::max(border, sm.part_floats);
-    const int sp = small_grid_splits(Cin, npix, Kp);
-    if (sp <= 1) return border;
-    const int kps = jp_cdiv(jp_cdiv(Kp, sp), KC) * KC;
-    return std::max(border, (long)jp_cdiv(Kp, kps) * Cin * npix);
+    if (p9sm_wanted(Cin, Cout, N, H, W, KH, stride, pad, &sm)) need = std::max(need, sm.part_floats);
+    const int sp = g.small_grid();
+    if (sp > 1) need = std::max(need, (long)k_slices(g.Kp, sp).n * Cin * g.npix);
+    return need;
 }
 
-// reflection border pass of a dgrad (rows of `a` = the C input channels of this call): through caller scratch when there is some
-// (K slices stored coalesced, one fixed-order fold into dx), else the read-modify-write epilogue
-static void border_pass(const PackA& a, const float* dy, float* dx, int C, int Cp, int Kp, int Cout, int N, int H, int W,
-                        float* split_ws, const JpCall& st) {
-    const int Nb = N * (2 * W + 2 * H);
-    DgradBorderB<3> bb{dy, Cp, Nb, H, W, Cout};
-    const long btiles = (long)jp_cdiv(C, C <= 64 ? 64 : 128) * jp_cdiv(Nb, C <= 64 ? 256 : 128);
-    static const bool via_ws = [] { const char* e_ = getenv("JP_BORDER_WS"); return !(e_ && e_[0] == '0'); }();
-    const int chunks = Kp / KC;
-    const int wsl = (int)std::max<long>(1, std::min<long>(std::min<long>(4, chunks / 9), jp_cdiv(512, btiles)));
-    if (via_ws && split_ws && wsl > 1) {      // (also the one-row launches -- the disparity channel: its slices met in float atomics until round 6)
-        const int wkps = jp_cdiv(jp_cdiv(Kp, wsl), KC) * KC, nsl = jp_cdiv(Kp, wkps);
+// ---- ring passes
+// reflection border pass of a dgrad (rows of `a` = the C input channels of this call).  The fold reports max |final value| of the
+// pixels it touches into the slot the main pass reported into (every element of dx is then covered by one of the two); the
+// read-modify-write epilogue does not report: the caller reduces dx itself
+static void border_pass(const PackA& a, const float* dy, float* dx, int C, const DgradGeom& g, const RingPlan& p, float* split_ws,
+                        const JpCall& st) {
+    const int Nb = g.ring(g.H, g.W);
+    DgradBorderB<3> bb{dy, g.Cp, Nb, g.H, g.W, g.Cout};
+    if (p.scratch) {      // (also the one-row launches -- the disparity channel)
         WgradEpiWS es{split_ws, C, Nb};
-        launch_auto(a, bb, es, C, Nb, Kp, nsl, wkps, st);
+        launch_auto(a, bb, es, C, Nb, g.Kp, p.sl.n, p.sl.kps, st);
         const long total = (long)C * Nb;
-        hipLaunchKernelGGL(border_add_kernel, dim3((int)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, split_ws, dx, C, Nb, H,
-                           W, nsl, (st.ax && st.ax->out_taken) ? st.ax->out : nullptr);
+        hipLaunchKernelGGL(border_add_kernel, dim3((int)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, split_ws, dx, C, Nb, g.H,
+                           g.W, p.sl.n, (st.ax && st.ax->out_taken) ? st.ax->out : nullptr);
         return;
     }
-    if (st.ax) st.ax->out_taken = false;       // (the read-modify-write epilogue below does not report: the caller reduces dx itself)
-    DgradBorderEpi be{dx, C, H, W, Nb, 0};
-    const int bsp = border_splits(btiles, Kp / KC);
-    const int bkps = jp_cdiv(jp_cdiv(Kp, bsp), KC) * KC;
-    be.split = jp_cdiv(Kp, bkps) > 1;
-    launch_auto(a, bb, be, C, Nb, Kp, jp_cdiv(Kp, bkps), bkps, st);
+    if (st.ax) st.ax->out_taken = false;
+    DgradBorderEpi be{dx, C, g.H, g.W, Nb, p.sl.n > 1};
+    launch_auto(a, bb, be, C, Nb, g.Kp, p.sl.n, p.sl.kps, st);
+}
+// edge pass of the upsampled segment (rows of `a` = its C channels, [16][C][Cp] pack): the clamp-folded entries of the boundary lines.
+// Through scratch the slices never meet in float atomics (run-dependent last bits in the gradient of the upsampled segment, which the
+// whole coarser decoder level inherits)
+static void edge_pass(const PackA& a, const float* dy, float* dx, int C, const DgradGeom& g, const RingPlan& p, float* split_ws,
+                      const JpCall& st) {
+    const int h2 = g.H / 2, w2 = g.W / 2, Nb = g.ring(h2, w2), KpU = 16 * g.Cp;
+    DgradUPBorderB bb{dy, Nb, h2, w2, g.Cout};
+    if (p.scratch) {
+        WgradEpiWS es{split_ws, C, Nb};
+        launch_auto(a, bb, es, C, Nb, KpU, p.sl.n, p.sl.kps, st);
+        const long total = (long)C * Nb;
+        hipLaunchKernelGGL(edge_add_kernel, dim3((int)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, split_ws, dx, C, Nb, h2,
+                           w2, p.sl.n);
+        return;
+    }
+    DgradEdgeEpi be{dx, C, h2, w2, Nb, p.sl.n > 1};
+    launch_auto(a, bb, be, C, Nb, KpU, p.sl.n, p.sl.kps, st);
 }
 
-// rows of a short row tail, 0 = none: 513 = 4*128 + 1 input channels of the iconv layers run the tail as its own 64-row launch
-// instead of a fifth, almost empty 128-row tile column
-static inline int dgrad_row_tail(int Cin) { return (Cin > 128 && Cin % 128 <= 16) ? Cin % 128 : 0; }
+// ---- launch sites
+// main pass over M rows of a full-resolution 3x3 stride-1 bank (DG_P9, DG_ROW_TILE) or of any bank (DG_TAP): `a` = the rows' slice of
+// the bank's tap-major pack, wfr = the bank's fragment-order pack, of which the rows start at M tile mt_off
+template <class B>
+static void main_pass(DgradKind kind, const PackA& a, const float* wfr, int mt_off, B b, DgradEpi e, int M, const DgradGeom& g,
+                      const float* dy, const JpCall& st) {
+    const int npix = (int)g.npix;
+    if (kind == DG_P9) {
+        launch_p9<false, true>(wfr, dy, e, M, g.Cout, g.N, g.H, g.W, st, mt_off, g.Cin);
+    } else if (kind == DG_ROW_TILE) {      // (taps mirrored, zero fill; the reflection fold stays with the border pass)
+        const Src3 sdy = make_src(dy, g.Cout, 0, nullptr, 0, 0, nullptr, 0, 0, g.H, g.W);
+        if (M <= 64) { FwdBR3<false, true, 256> b3{sdy, g.H, g.W}; launch_r3<1, 4>(a, b3, e, M, npix, g.Kp, st); }
+        else { FwdBR3<false, true, 128> b3{sdy, g.H, g.W}; launch_r3<2, 2>(a, b3, e, M, npix, g.Kp, st); }
+    } else {
+        launch_auto(a, b, e, M, npix, g.Kp, 1, g.Kp, st);
+    }
+}
+// DG_P9 / DG_ROW_TILE / DG_TAP of jp_conv2d_dgrad: the main pass over r.Mm rows, then the row tail
+static int run_rows(const DgradGeom& g, const DgradRoute& r, const PackA& a, const float* wfr, const float* dy, float* dx, int accumulate,
+                    const DgradEpi& e, const JpCall& st) {
+    const int npix = (int)g.npix, HW = g.H * g.W;
+    auto go = [&](auto b) {
+        main_pass(r.kind, a, wfr, 0, b, e, r.Mm, g, dy, st);
+        if (!r.tail) return;
+        PackA at{a.wp + (size_t)r.Mm * g.Cp, g.Cin, g.Kp, g.Cp, g.KK()};
+        DgradEpi et{dx + (size_t)r.Mm * HW, g.Cin, HW, accumulate};
+        launch_auto(at, b, et, r.tail, npix, g.Kp, 1, g.Kp, st);
+    };
+    JP_KH_SWITCH(g.KH, {
+        if (g.stride == 1) go(DgradBT<KH_, true>{dy, g.Cp, npix, g.H, g.W, g.Cout, g.OH, g.OW, g.stride, g.pad, g.reflect()});
+        else go(DgradBT<KH_>{dy, g.Cp, npix, g.H, g.W, g.Cout, g.OH, g.OW, g.stride, g.pad, g.reflect()});
+    });
+    return JP_OK;
+}
+// DG_SPLIT_SCRATCH / DG_SPLIT_ATOMIC
+static int run_split(const DgradGeom& g, const DgradRoute& r, const PackA& a, const float* dy, float* dx, int accumulate, float* split_ws,
+                     const JpCall& st) {
+    const int npix = (int)g.npix, HW = g.H * g.W;
+    const bool scratch = r.kind == DG_SPLIT_SCRATCH;
+    if (!scratch && !accumulate) JP_HIP(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)npix * g.Cin, st));
+    JP_KH_SWITCH(g.KH, {
+        DgradBT<KH_> b{dy, g.Cp, npix, g.H, g.W, g.Cout, g.OH, g.OW, g.stride, g.pad, g.reflect()};
+        if (scratch) launch_auto(a, b, WgradEpiWS{split_ws, g.Cin, npix}, g.Cin, npix, g.Kp, r.sl.n, r.sl.kps, st);
+        else launch_auto(a, b, AtomicEpi{dx, g.Cin, HW}, g.Cin, npix, g.Kp, r.sl.n, r.sl.kps, st);
+    });
+    if (scratch) slice_reduce_nchw(split_ws, dx, nullptr, g.Cin, npix, HW, r.sl.n, JP_ACT_NONE, accumulate, st);
+    return JP_OK;
+}
+static void run_p9s2d(const DgradGeom& g, int bmt, const float* wfr, const float* dy, const DgradEpi& e, const JpCall& st) {
+    const int N = g.N, Cin = g.Cin, Cout = g.Cout, OH = g.OH, OW = g.OW, NST = Cout / 16;
+    const unsigned* wq = reinterpret_cast<const unsigned*>(wfr);
+    const float* xam = JP_NS == 2 ? jp_amax_of(dy, (long)N * Cout * OH * OW, st) : nullptr;
+    jp_prof_before(bmt == 64 ? p9s2d_tag<1, 4, DgradEpi>() : p9s2d_tag<2, 2, DgradEpi>(), JP_NPROD * 2.0 * Cin * (double)N * OH * OW * 9.0 * Cout,
+                   st);
+    if (bmt == 64)
+        hipLaunchKernelGGL((jp_igemm_p9s2d_kernel<1, 4, 2, DgradEpi>), dim3(4 * N * (OH / 8) * (OW / 32), 1, 1), dim3(256), 0, st, wq, dy, e,
+                           Cin, Cout, NST, OH, OW, xam);
+    else
+        hipLaunchKernelGGL((jp_igemm_p9s2d_kernel<2, 2, 2, DgradEpi>), dim3(4 * N * (OH / 4) * (OW / 32), jp_cdiv(Cin, 128), 1), dim3(256), 0,
+                           st, wq, dy, e, Cin, Cout, NST, OH, OW, xam);
+    jp_prof_after(st);
+}
+static int run_channel_major(const DgradGeom& g, const float* dy, const float* w, const DgradEpi& e, const JpCall& st) {
+    const int K = g.Cout * g.KK(), npix = (int)g.npix;
+    JP_KH_SWITCH(g.KH, {
+        DgradA<KH_> a{w, g.Cin, K};
+        DgradB<KH_> b{dy, K, npix, g.H, g.W, g.Cout, g.OH, g.OW, g.stride, g.pad, g.reflect()};
+        launch_auto(a, b, e, g.Cin, npix, K, 1, jp_cdiv(K, KC) * KC, st);
+    });
+    return JP_OK;
+}
 
 extern "C" int jp_conv2d_dgrad(const float* dy, const float* w, float* dx, int N, int Cin, int H, int W, int Cout,
                                int KH, int stride, int pad, int pad_mode, int accumulate, float* ws, int ws_state,
@@ -701,155 +956,63 @@ extern "C" int jp_conv2d_dgrad(const float* dy, const float* w, float* dx, int N
     JP_CHECK_ARG(dy && w && dx, "conv2d_dgrad: null pointer");
     JP_CHECK_ARG(!(pad_mode == JP_PAD_REFLECT && !(KH == 3 && stride == 1 && pad == 1 && H >= 2 && W >= 2)),
                  "conv2d_dgrad: reflect mode supports 3x3 stride 1 pad 1 only");
-    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
-    const long npix = (long)N * H * W;
-    JP_CHECK_ARG(npix < (1L << 31), "conv2d_dgrad: tensor too large");
+    const DgradGeom g = dgrad_geom(N, Cin, H, W, Cout, KH, stride, pad, pad_mode, ws != nullptr, split_ws != nullptr);
+    JP_CHECK_ARG(g.npix < (1L << 31), "conv2d_dgrad: tensor too large");
     JP_CHECK_ARG(JP_NS != 2 || amax_ws || amax_dy, "conv2d_dgrad"": every operand magnitude (amax_*) or amax_ws (jp_conv2d_amax_ws_floats floats of scratch) must be given");
     JpAmaxCtx ax;
     ax.know(dy, amax_dy);
     ax.ws = amax_ws;
     // amax_dx: folded in by the patch kernels' epilogue (+ the border fold of reflection layers); a layer with a short row tail is
     // finished by a second launch that does not report, so the slot is not offered there
-    if (!dgrad_row_tail(Cin)) ax.out = reinterpret_cast<unsigned*>(amax_dx);
+    if (!g.tail()) ax.out = reinterpret_cast<unsigned*>(amax_dx);
     const JpAmaxDone done_flag{amax_dx_done, &ax};
     const JpCall st((hipStream_t)stream, &ax);
-    if (jp_c16_ok(Cin, Cout, KH, stride, pad, pad_mode, H, W)) {
-        jp_c16_dgrad(dy, w, dx, 0, N, Cin, Cout, H, W, accumulate, st);
-        JP_LAUNCH_CHECK();
+    const DgradRoute r = dgrad_route(g);
+    const int OH = g.OH, OW = g.OW, Cp = g.Cp, npix = (int)g.npix;
+    float* wfr = ws ? ws + dgrad_tap_floats(Cin, Cout, KH) : nullptr;       // the fragment-order pack sits behind the tap-major one
+    if (!ws_state) {
+        if (r.pack_tap) pack_weights(w, ws, Cout, Cin, g.KK(), Cp, 1, st);
+        if (r.frag_bmt) pack_p9(w, wfr, Cout, Cin, 1, r.frag_bmt, r.frag_khw, st);
     }
-    DgradEpi e{dx, Cin, H * W, accumulate};
-    if (ws && Cout >= 16) {
-        const int Cp = pad32(Cout), Kp = KH * KH * Cp;
-        const int sp = small_grid_splits(Cin, npix, Kp);
-        // zero-padded 3x3 stride-1 layers that the P9 main pass covers completely (no row tail, no reflection border pass)
-        // never read the tap-major pack: it is neither built nor replayed for them
-        const bool p9_only = KH == 3 && stride == 1 && pad == 1 && pad_mode != JP_PAD_REFLECT && sp <= 1 &&
-                             !dgrad_row_tail(Cin) && p9_ok(Cin, Cout, N, H, W);
-        const long Nc = (long)N * (H / 2) * (W / 2);
-        // 3x3 stride-2 layers: class-uniform split-bf16 kernel on the half-resolution grid (its own fragment-order pack only)
-        const bool s2_form = KH == 3 && stride == 2 && pad == 1 && pad_mode != JP_PAD_REFLECT && H % 2 == 0 && W % 2 == 0 &&
-                             2 * OH == H && 2 * OW == W;
-        if (s2_form && p9s_enabled() && p9s2_enabled() && JP_ENV_ON("JP_P9S2D") && Cin >= 32 && Cout % 16 == 0 && OW % 32 == 0 &&
-            OH % (Cin <= 64 ? 8 : 4) == 0 && (long)N * Cout * OH * OW * 4 < (1L << 31) &&
-            (long)jp_cdiv(Cin, Cin <= 64 ? 64 : 128) * N * (OH / (Cin <= 64 ? 8 : 4)) * (OW / 32) * 4 >= 192) {
-            float* wfr = ws + dgrad_tap_floats(Cin, Cout, KH);
-            const int bmt = Cin <= 64 ? 64 : 128;
-            if (!ws_state) pack_p9(w, wfr, Cout, Cin, 1, bmt, 9, st);
-            const unsigned* wq = reinterpret_cast<const unsigned*>(wfr);
-            const int NST = Cout / 16;
-            const float* xam = JP_NS == 2 ? jp_amax_of(dy, (long)N * Cout * OH * OW, st) : nullptr;
-            jp_prof_before(bmt == 64 ? p9s2d_tag<1, 4, DgradEpi>() : p9s2d_tag<2, 2, DgradEpi>(),
-                           JP_NPROD * 2.0 * Cin * (double)N * OH * OW * 9.0 * Cout, st);
-            if (bmt == 64)
-                hipLaunchKernelGGL((jp_igemm_p9s2d_kernel<1, 4, 2, DgradEpi>), dim3(4 * N * (OH / 8) * (OW / 32), 1, 1), dim3(256), 0, st,
-                                   wq, dy, e, Cin, Cout, NST, OH, OW, xam);
-            else
-                hipLaunchKernelGGL((jp_igemm_p9s2d_kernel<2, 2, 2, DgradEpi>), dim3(4 * N * (OH / 4) * (OW / 32), jp_cdiv(Cin, 128), 1),
-                                   dim3(256), 0, st, wq, dy, e, Cin, Cout, NST, OH, OW, xam);
-            jp_prof_after(st);
-            JP_LAUNCH_CHECK();
-        }
-        if (KH == 1 && stride == 2 && pad == 0 && H % 2 == 0 && W % 2 == 0 && 2 * OH == H && 2 * OW == W && p1s2_ok(Cin, Cout, N, OH, OW)) {
-            // 1x1 stride 2: the stride-1 1x1 kernel over the half-resolution dY, scattering epilogue
-            float* wfr = ws + dgrad_tap_floats(Cin, Cout, KH);
-            const int bmt = p9_bmt(Cin, 1, p9_ptiles(N, OH, OW));
-            if (!ws_state) pack_p9(w, wfr, Cout, Cin, 1, bmt, 1, st);
+    const PackA a{ws, Cin, g.Kp, Cp, g.KK()};
+    const DgradEpi e{dx, Cin, H * W, accumulate};
+    int rc = JP_OK;
+    switch (r.kind) {
+        case DG_C16: rc = jp_c16_dgrad(dy, w, dx, 0, N, Cin, Cout, H, W, accumulate, st); break;
+        case DG_P9S2D: run_p9s2d(g, r.frag_bmt, wfr, dy, e, st); break;
+        case DG_P1S2: {
             DgradS2PointEpi ep{dx, Cin, OH * OW, OW, accumulate};
-            launch_p9s<false, false, DgradS2PointEpi, 1>(wfr, dy, ep, Cin, Cout, N, OH, OW, st, 0, bmt);
-            JP_LAUNCH_CHECK();
-        }
-        if (!ws_state && !p9_only) pack_weights(w, ws, Cout, Cin, KH * KH, Cp, 1, st);
-        PackA a{ws, Cin, Kp, Cp, KH * KH};
-        if (KH == 3 && stride == 2 && pad == 1 && pad_mode != JP_PAD_REFLECT && H % 2 == 0 && W % 2 == 0 && Nc % 256 == 0 &&
-            2 * OH == H && 2 * OW == W) {
-            // parity-class form: 4 tap slots instead of 9 taps per input pixel
-            PackAS2 a2{ws, Cin, Cp, (int)Nc};
-            DgradS2B b2{dy, Cp, (int)Nc, H / 2, W / 2, Cout, OH, OW};
-            DgradS2Epi e2{dx, Cin, (int)Nc, H / 2, W / 2, accumulate};
-            launch_auto(a2, b2, e2, Cin, (int)npix, 4 * Cp, 1, 4 * Cp, st);
-            JP_LAUNCH_CHECK();
-        }
-        JpP9smPlan sm;
-        if (!dgrad_row_tail(Cin) && !(sp <= 1 && p9_only) && p9sm_wanted(Cin, Cout, N, H, W, KH, stride, pad, &sm) && (sm.splits == 1 || split_ws)) {
-            // small maps: main pass on the split-bf16 patch kernel (taps mirrored, zero fill), then the reflection fold as usual
-            float* wfr = ws + dgrad_tap_floats(Cin, Cout, KH);
-            if (!ws_state) pack_p9(w, wfr, Cout, Cin, 1, sm.bmt, KH * KH, st);
-            jp_p9sm_launch(sm, wfr, dy, dx, nullptr, JP_ACT_NONE, accumulate, split_ws, Cin, Cout, N, H, W, KH * KH, 0, 1, st);
-            if (sm.splits > 1) slice_reduce_nchw(split_ws, dx, nullptr, Cin, (int)npix, H * W, sm.splits, JP_ACT_NONE, accumulate, st);
-        } else
-        if (sp > 1 && split_ws) {   // small grids: K slices to scratch, fixed-order reduction (no memset, no atomics)
-            const int kps = jp_cdiv(jp_cdiv(Kp, sp), KC) * KC;
-            WgradEpiWS es{split_ws, Cin, (int)npix};
-            JP_KH_SWITCH(KH, {
-                DgradBT<KH_> b{dy, Cp, (int)npix, H, W, Cout, OH, OW, stride, pad, pad_mode == JP_PAD_REFLECT};
-                launch_auto(a, b, es, Cin, (int)npix, Kp, jp_cdiv(Kp, kps), kps, st);
-            });
-            slice_reduce_nchw(split_ws, dx, nullptr, Cin, (int)npix, H * W, jp_cdiv(Kp, kps), JP_ACT_NONE, accumulate, st);
-        } else if (sp > 1) {
-            const int kps = jp_cdiv(jp_cdiv(Kp, sp), KC) * KC;
-            if (!accumulate) JP_HIP(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)npix * Cin, st));
-            AtomicEpi ea{dx, Cin, H * W};
-            JP_KH_SWITCH(KH, {
-                DgradBT<KH_> b{dy, Cp, (int)npix, H, W, Cout, OH, OW, stride, pad, pad_mode == JP_PAD_REFLECT};
-                launch_auto(a, b, ea, Cin, (int)npix, Kp, jp_cdiv(Kp, kps), kps, st);
-            });
-        } else {
-            // the main launch covers the first Mm rows; a row tail is finished by its own launch on the same pack
-            const int tail = dgrad_row_tail(Cin), Mm = Cin - tail;
-            auto launch_tail = [&](auto b) {
-                if (!tail) return;
-                PackA at{ws + (size_t)Mm * Cp, Cin, Kp, Cp, KH * KH};
-                DgradEpi et{dx + (size_t)Mm * H * W, Cin, H * W, accumulate};
-                launch_auto(at, b, et, tail, (int)npix, Kp, 1, Kp, st);
-            };
-            if (stride == 1) {
-                JP_KH_SWITCH(KH, {
-                    DgradBT<KH_, true> b{dy, Cp, (int)npix, H, W, Cout, OH, OW, stride, pad, pad_mode == JP_PAD_REFLECT};
-                    const int bn3 = Mm <= 64 ? 256 : 128;
-                    if (KH == 1 && pad == 0 && tail == 0 && p9_ok(Cin, Cout, N, H, W, 1)) {
-                        float* wfr = ws + dgrad_tap_floats(Cin, Cout, KH);
-                        if (!ws_state) pack_p9(w, wfr, Cout, Cin, 1, p9_bmt(Cin, 1, p9_ptiles(N, H, W)), 1, st);
-                        launch_p1(wfr, dy, e, Cin, Cout, N, H, W, st);
-                    } else
-                    if (KH == 3 && pad == 1 && (tail == 0 || Mm > 64) && p9_ok(Mm, Cout, N, H, W)) {
-                        // P9 patch kernel on dY (taps mirrored, zero fill; the reflection fold stays with the border pass);
-                        // fragment-order pack behind the tap-major one (which the border pass still reads).  With a short
-                        // row tail (513 = 4*128 + 1) the kernel runs the full 128-row tiles of the same pack, the tail
-                        // its own launch below.
-                        float* wfr = ws + dgrad_tap_floats(Cin, Cout, KH);
-                        if (!ws_state) pack_p9(w, wfr, Cout, Cin, 1, p9_bmt(Cin, 9, p9_ptiles(N, H, W)), 9, st);
-                        launch_p9<false, true>(wfr, dy, e, Mm, Cout, N, H, W, st, 0, Cin);
-                    } else
-                    if (KH == 3 && pad == 1 && Cout >= 32 && W % bn3 == 0 && npix > 64) {
-                        // row-tile kernel on dY (taps mirrored, zero fill; the reflection fold stays with the border pass)
-                        const Src3 sdy = make_src(dy, Cout, 0, nullptr, 0, 0, nullptr, 0, 0, H, W);
-                        if (Mm <= 64) { FwdBR3<false, true, 256> b3{sdy, H, W}; launch_r3<1, 4>(a, b3, e, Mm, (int)npix, Kp, st); }
-                        else { FwdBR3<false, true, 128> b3{sdy, H, W}; launch_r3<2, 2>(a, b3, e, Mm, (int)npix, Kp, st); }
-                    } else
-                    launch_auto(a, b, e, Mm, (int)npix, Kp, 1, Kp, st);
-                    launch_tail(b);
-                });
-            } else
-            JP_KH_SWITCH(KH, {
-                DgradBT<KH_> b{dy, Cp, (int)npix, H, W, Cout, OH, OW, stride, pad, pad_mode == JP_PAD_REFLECT};
-                launch_auto(a, b, e, Mm, (int)npix, Kp, 1, Kp, st);
-                launch_tail(b);
-            });
-        }
-        if (pad_mode == JP_PAD_REFLECT)     // fold the reflected ring back in (border-adjacent lines only)
-            border_pass(a, dy, dx, Cin, Cp, Kp, Cout, N, H, W, split_ws, st);
-    } else {
-        const int K = Cout * KH * KH;
-        JP_KH_SWITCH(KH, {
-            DgradA<KH_> a{w, Cin, K};
-            DgradB<KH_> b{dy, K, (int)npix, H, W, Cout, OH, OW, stride, pad, pad_mode == JP_PAD_REFLECT};
-            launch_auto(a, b, e, Cin, (int)npix, K, 1, jp_cdiv(K, KC) * KC, st);
-        });
+            launch_p9s<false, false, DgradS2PointEpi, 1>(wfr, dy, ep, Cin, Cout, N, OH, OW, st, 0, r.frag_bmt);
+        } break;
+        case DG_S2_PARITY: {
+            const int Nc = (int)g.Nc();
+            PackAS2 a2{ws, Cin, Cp, Nc};
+            DgradS2B b2{dy, Cp, Nc, H / 2, W / 2, Cout, OH, OW};
+            DgradS2Epi e2{dx, Cin, Nc, H / 2, W / 2, accumulate};
+            launch_auto(a2, b2, e2, Cin, npix, 4 * Cp, 1, 4 * Cp, st);
+        } break;
+        case DG_P9SM:
+            jp_p9sm_launch(r.sm, wfr, dy, dx, nullptr, JP_ACT_NONE, accumulate, split_ws, Cin, Cout, N, H, W, g.KK(), 0, 1, st);
+            if (r.sm.splits > 1) slice_reduce_nchw(split_ws, dx, nullptr, Cin, npix, H * W, r.sm.splits, JP_ACT_NONE, accumulate, st);
+            break;
+        case DG_SPLIT_SCRATCH:
+        case DG_SPLIT_ATOMIC: rc = run_split(g, r, a, dy, dx, accumulate, split_ws, st); break;
+        case DG_P1: launch_p1(wfr, dy, e, Cin, Cout, N, H, W, st); break;
+        case DG_P9:
+        case DG_ROW_TILE:
+        case DG_TAP: rc = run_rows(g, r, a, wfr, dy, dx, accumulate, e, st); break;
+        case DG_CHANNEL_MAJOR: rc = run_channel_major(g, dy, w, e, st); break;
+        default:      // (dgrad_src3_route's kinds)
+            jp_set_last_error("conv2d_dgrad: internal: not a kind of dgrad_route");
+            rc = JP_EBADARG;
+            break;
     }
+    if (rc) return rc;
+    if (r.border) border_pass(a, dy, dx, Cin, g, r.ring, split_ws, st);      // fold the reflected ring back in (border-adjacent lines only)
     JP_LAUNCH_CHECK();
 }
 
-// per-source dgrad of a conv whose input is the channel concat of up to 3 sources, one of them read through the fused
+// ---- per-source dgrad of a conv whose input is the channel concat of up to 3 sources, one of them read through the fused
 // nearest-2x upsample: gradients go straight into the sources' own buffers (dx_s: (N, c_s, H, W), or (N, c_s, H/2, W/2)
 // for the upsampled one; NULL = not needed; acc_s: add instead of overwrite) -- no concat-sized gradient tensor.
 static bool dgrad_segments_ok(int c0, int up0, int c1, int up1, int c2, int up2, int N, int H, int W, int Cout, int KH,
@@ -866,124 +1029,156 @@ extern "C" int jp_conv2d_dgrad_src3_ok(int c0, int up0, int c1, int up1, int c2,
     if (up_head(c0, up0, c1, c2, Cout, KH, stride, pad, pad_mode, H, W)) return 1;
     return dgrad_segments_ok(c0, up0, c1, up1, c2, up2, N, H, W, Cout, KH, stride, pad, pad_mode) ? 1 : 0;
 }
-// scratch for jp_conv2d_dgrad_src3's `split_ws`: <= 4 K slices of the widest full-resolution segment's border pass
+// scratch for jp_conv2d_dgrad_src3's `split_ws` (the rule of the queries above: it has no Cout, so both ring passes at their caps):
+// the border pass of the widest full-resolution segment, the edge pass of the upsampled one over the N * (H + W) half-resolution pixels
 extern "C" long jp_conv2d_dgrad_src3_split_floats(int c0, int up0, int c1, int up1, int c2, int up2, int N, int H, int W) {
     const int cm = std::max(std::max(up0 ? 0 : c0, up1 ? 0 : c1), up2 ? 0 : c2);
     const int cu = std::max(std::max(up0 ? c0 : 0, up1 ? c1 : 0), up2 ? c2 : 0);
-    // <= 4 slices of a full-resolution segment's border pass, <= 8 slices of the upsampled segment's edge pass (N * (H + W) pixels)
-    return std::max(4L * cm * N * (2L * H + 2L * W), 8L * cu * N * ((long)H + W));
+    return std::max((long)BORDER_RING.cap * cm * N * (2L * H + 2L * W), (long)EDGE_RING.cap * cu * N * ((long)H + W));
 }
 
-extern "C" int jp_conv2d_dgrad_src3(const float* dy, const float* w, float* dx0, int c0, int up0, int acc0, float* dx1,
-                                    int c1, int up1, int acc1, float* dx2, int c2, int up2, int acc2, int N, int H, int W,
-                                    int Cout, int KH, int stride, int pad, int pad_mode, float* ws, int ws_state,
-                                    float* split_ws, const float* amax_dy, float* amax_dx0, int* amax_dx0_done, float* amax_ws,
-                                    void* stream) {
-    if (amax_dx0_done) *amax_dx0_done = 0;
-    // split_ws: optional scratch of jp_conv2d_dgrad_src3_split_floats floats for the border passes (NULL: read-modify-write epilogue)
-    JP_CHECK_ARG(dy && w, "conv2d_dgrad_src3: null pointer");
-    if (up_head(c0, up0, c1, c2, Cout, KH, stride, pad, pad_mode, H, W)) {
-        if (dx0) jp_up_head_dgrad(dy, w, dx0, N, c0, H / 2, W / 2, acc0, (hipStream_t)stream);
-        JP_LAUNCH_CHECK();
-    }
-    JP_CHECK_ARG(ws != nullptr, "conv2d_dgrad_src3: null scratch");
-    JP_CHECK_ARG(dgrad_segments_ok(c0, up0, c1, up1, c2, up2, N, H, W, Cout, KH, stride, pad, pad_mode),
-                 "conv2d_dgrad_src3: shape not supported (check jp_conv2d_dgrad_src3_ok)");
-    JP_CHECK_ARG(JP_NS != 2 || amax_ws || amax_dy, "conv2d_dgrad_src3"": every operand magnitude (amax_*) or amax_ws (jp_conv2d_amax_ws_floats floats of scratch) must be given");
-    JpAmaxCtx ax;
-    ax.know(dy, amax_dy);
-    ax.ws = amax_ws;
-    const JpCall st((hipStream_t)stream, &ax);
-    const int Cin = c0 + c1 + c2, Cp = pad32(Cout), Kp = 9 * Cp;
-    const long npix = (long)N * H * W;
-    float* dxs[3] = {dx0, dx1, dx2};
-    const int cs[3] = {c0, c1, c2}, us[3] = {up0, up1, up2}, accs[3] = {acc0, acc1, acc2};
-    if (!ws_state) pack_weights(w, ws, Cout, Cin, 9, Cp, 1, st);  // [tap][ci][Cp] for the full-resolution segments
-    float* wsT = ws + ((size_t)9 * Cin + 256) * Cp;               // [16][Cx][Cp] for the upsampled one
-    const int cx_up = up0 ? c0 : (up1 ? c1 : c2);
-    DgradBT<3, true> b{dy, Cp, (int)npix, H, W, Cout, H, W, 1, 1, 1};
+struct SegRoute {
+    DgradKind kind;         // DG_NONE: no channels, or the gradient is not wanted
+    int C, coff, up;        // channels, first row in the bank, read through the upsample
+    RingPlan ring;          // the border pass (full resolution) or the edge pass (upsampled) behind the main pass
+};
+struct Src3Route {
+    bool up_head;           // the whole call is the one-channel head on one upsampled source (conv_small.hip)
+    bool segments;          // or one pass per source (dgrad_segments_ok); neither: the entry point refuses the shape
+    SegRoute seg[3];
+    int cx_up;              // channels of the upsampled source
+    long split_use;
+};
+// g: the bank (all sources' channels); want[i]: source i's gradient buffer was given
+static Src3Route dgrad_src3_route(const DgradGeom& g, const int* cs, const int* us, const bool* want) {
+    Src3Route r{};
+    r.up_head = up_head(cs[0], us[0], cs[1], cs[2], g.Cout, g.KH, g.stride, g.pad, g.pad_mode, g.H, g.W);
+    r.segments = !r.up_head && dgrad_segments_ok(cs[0], us[0], cs[1], us[1], cs[2], us[2], g.N, g.H, g.W, g.Cout, g.KH, g.stride, g.pad, g.pad_mode);
+    if (!r.segments) return r;
+    const int N = g.N, H = g.H, W = g.W, Cout = g.Cout, h2 = H / 2, w2 = W / 2;
+    const int bmt = p9_bmt(g.Cin, 9, p9_ptiles(N, H, W));     // M tile of the whole bank's fragment-order pack
     int coff = 0;
+    for (int i = 0; i < 3; coff += cs[i++]) {
+        const int C = cs[i];
+        SegRoute& s = r.seg[i];
+        s = SegRoute{DG_NONE, C, coff, us[i]};
+        if (us[i]) r.cx_up = C;
+        if (!C || !want[i]) continue;
+        if (us[i]) {
+            // split-product patch kernel over the full-resolution dY (igemm_p9sd.h), or the 16 (class, slot) GEMMs of DgradUPB
+            const bool sd = p9sd_enabled() && h2 % 4 == 0 && w2 % 32 == 0 && Cout % 16 == 0 && (long)N * Cout * H * W * 4 < (1L << 31) &&
+                            (long)jp_cdiv(C, 128) * N * (h2 / 4) * (w2 / 32) >= 192;
+            s.kind = sd ? DG_P9SD : DG_UP_TAP;
+            s.ring = edge_plan(g, C);
+            r.split_use = std::max(r.split_use, ring_floats(s.ring, C, g.ring(h2, w2)));
+            continue;
+        }
+        // a few channels (the disparity channel): direct zero-pad correlation of dY with the flipped taps instead of a 64-row MFMA tile
+        if (C <= 4 && (long)C * Cout * 9 * 4 <= 48 * 1024) s.kind = DG_SMALL;
+        // P9 patch kernel on this segment's tiles of the whole bank's fragment-order pack
+        else if (g.Cin > 64 && C > 64 && coff % bmt == 0 && p9_ok(C, Cout, N, H, W)) s.kind = DG_P9;
+        else s.kind = row_tile_ok(g, C) ? DG_ROW_TILE : DG_TAP;
+        s.ring = border_plan(g, C);
+        r.split_use = std::max(r.split_use, ring_floats(s.ring, C, g.ring(H, W)));
+    }
+    return r;
+}
+
+// the segments of r, one after the other: pack (ws_state == 0), main pass, ring pass.  Packs in `ws`: the bank's tap-major pack
+// [tap][ci][Cp]; behind it (+ slack) the upsampled segment's [16][Cx][Cp]; behind that (+ slack) the flipped taps of a DG_SMALL
+// segment; at dgrad_tap_floats the bank's fragment-order pack, built once for all DG_P9 segments, and behind it DG_P9SD's.
+// amax_dx0: max |dx0| out of the first source's passes (main patch kernel + border fold), if it is a full-resolution one.
+static int run_segments(const DgradGeom& g, const Src3Route& r, const float* dy, const float* w, float* const* dxs, const int* accs,
+                        float* ws, int ws_state, float* split_ws, float* amax_dx0, int* amax_dx0_done, JpAmaxCtx& ax, const JpCall& st) {
+    const int N = g.N, Cin = g.Cin, H = g.H, W = g.W, Cout = g.Cout, Cp = g.Cp, Kp = g.Kp, h2 = H / 2, w2 = W / 2, KpU = 16 * Cp;
+    const long np2 = (long)N * h2 * w2;
+    float* wsT = ws + ((size_t)9 * Cin + 256) * Cp;
+    float* wf = wsT + (16L * r.cx_up + 256) * Cp;
+    float* wfr = ws + dgrad_tap_floats(Cin, Cout, 3);
+    float* wsd = wfr + p9_alloc_floats(Cin, Cp);
+    const int bmt = p9_bmt(Cin, 9, p9_ptiles(N, H, W));
+    if (!ws_state) pack_weights(w, ws, Cout, Cin, 9, Cp, 1, st);
+    const DgradBT<3, true> b{dy, Cp, (int)g.npix, H, W, Cout, H, W, 1, 1, 1};
     bool frag_packed = false;
-    for (int sidx = 0; sidx < 3; ++sidx) {
-        const int C = cs[sidx];
-        if (!C) continue;
-        float* dx = dxs[sidx];
-        // amax_dx0: max |dx0| out of the first source's passes (main patch kernel + border fold), if it is a full-resolution one
-        ax.out = (sidx == 0 && !us[0]) ? reinterpret_cast<unsigned*>(amax_dx0) : nullptr;
+    for (int i = 0; i < 3; ++i) {
+        const SegRoute& s = r.seg[i];
+        if (s.kind == DG_NONE) continue;
+        const int C = s.C, coff = s.coff;
+        float* dx = dxs[i];
+        ax.out = (i == 0 && !s.up) ? reinterpret_cast<unsigned*>(amax_dx0) : nullptr;
         ax.out_taken = false;
-        if (dx && !us[sidx]) {
-            PackA a{ws + (size_t)coff * Cp, Cin, Kp, Cp, 9};
-            if (C <= 4 && (long)C * Cout * 9 * 4 <= 48 * 1024) {
-                // a few channels (the disparity channel): direct zero-pad correlation of dY with the flipped taps
-                // instead of a 64-row MFMA tile; the reflection fold still comes from the border pass below
-                float* wf = wsT + (16L * cx_up + 256) * Cp;     // behind the upsampled segment's pack (+ its slack)
-                if (!ws_state) do_pack(PACK_FLIP, w, wf, (long)C * Cout * 9, Cout, Cin, coff, C, 0, 0, st);
-                jp_conv_small_fwd(dy, Cout, 0, nullptr, 0, 0, nullptr, 0, 0, wf, nullptr, dx, N, H, W, C, JP_ACT_NONE, 0, st,
-                                  accs[sidx]);
-            } else {
-                DgradEpi e{dx, C, H * W, accs[sidx]};
-                const int bn3 = C <= 64 ? 256 : 128;
-                if (Cin > 64 && C > 64 && coff % p9_bmt(Cin, 9, p9_ptiles(N, H, W)) == 0 && p9_ok(C, Cout, N, H, W)) {
-                    // P9 patch kernel on this segment's 128-row tiles of the whole bank's fragment-order pack
-                    float* wfr = ws + dgrad_tap_floats(Cin, Cout, 3);
-                    if (!ws_state && !frag_packed) {
-                        pack_p9(w, wfr, Cout, Cin, 1, p9_bmt(Cin, 9, p9_ptiles(N, H, W)), 9, st);
-                        frag_packed = true;
-                    }
-                    launch_p9<false, true>(wfr, dy, e, C, Cout, N, H, W, st, coff / p9_bmt(Cin, 9, p9_ptiles(N, H, W)), Cin);
-                } else
-                if (W % bn3 == 0 && Cout >= 32) {     // row-tile kernel, see jp_conv2d_dgrad
-                    const Src3 sdy = make_src(dy, Cout, 0, nullptr, 0, 0, nullptr, 0, 0, H, W);
-                    if (C <= 64) { FwdBR3<false, true, 256> b3{sdy, H, W}; launch_r3<1, 4>(a, b3, e, C, (int)npix, Kp, st); }
-                    else { FwdBR3<false, true, 128> b3{sdy, H, W}; launch_r3<2, 2>(a, b3, e, C, (int)npix, Kp, st); }
-                } else {
-                    launch_auto(a, b, e, C, (int)npix, Kp, 1, Kp, st);
-                }
-            }
-            border_pass(a, dy, dx, C, Cp, Kp, Cout, N, H, W, split_ws, st);
-            if (sidx == 0 && amax_dx0_done) *amax_dx0_done = ax.out_taken ? 1 : 0;
-        } else if (dx) {
-            const int h2 = H / 2, w2 = W / 2, KpU = 16 * Cp;
-            const long tot = 16L * C * Cp, np2 = (long)N * h2 * w2;
-            if (!ws_state) do_pack(PACK_UP_DGRAD, w, wsT, tot, Cout, Cin, coff, C, Cp, 0, st);
-            PackA a{wsT, C, KpU, Cp, 16};
-            DgradUPB bu{dy, (int)np2, h2, w2, Cout};
-            DgradEpi e{dx, C, h2 * w2, accs[sidx]};
-            if (p9sd_enabled() && h2 % 4 == 0 && w2 % 32 == 0 && Cout % 16 == 0 && (long)N * Cout * H * W * 4 < (1L << 31) &&
-                (long)jp_cdiv(C, 128) * N * (h2 / 4) * (w2 / 32) >= 192) {
-                // split-product patch kernel over the full-resolution dY (igemm_p9sd.h); its pack sits behind the P9 one
-                float* wsd = ws + dgrad_tap_floats(Cin, Cout, 3) + p9_alloc_floats(Cin, Cp);
-                if (!ws_state) do_pack(PACK_SPLITUPD, w, wsd, p9sd_floats(C, Cout), Cout, Cin, coff, C, 0, 0, st);
+        const PackA a = s.up ? PackA{wsT, C, KpU, Cp, 16} : PackA{ws + (size_t)coff * Cp, Cin, Kp, Cp, 9};
+        const DgradEpi e{dx, C, s.up ? h2 * w2 : H * W, accs[i]};
+        if (!ws_state) switch (s.kind) {
+            case DG_SMALL: do_pack(PACK_FLIP, w, wf, (long)C * Cout * 9, Cout, Cin, coff, C, 0, 0, st); break;
+            case DG_P9:
+                if (!frag_packed) pack_p9(w, wfr, Cout, Cin, 1, bmt, 9, st);
+                frag_packed = true;
+                break;
+            case DG_P9SD:
+            case DG_UP_TAP:     // (the edge pass reads the [16][Cx][Cp] pack behind either)
+                do_pack(PACK_UP_DGRAD, w, wsT, 16L * C * Cp, Cout, Cin, coff, C, Cp, 0, st);
+                if (s.kind == DG_P9SD) do_pack(PACK_SPLITUPD, w, wsd, p9sd_floats(C, Cout), Cout, Cin, coff, C, 0, 0, st);
+                break;
+            default: break;
+        }
+        int rc = JP_OK;
+        switch (s.kind) {
+            case DG_SMALL:      // (the reflection fold still comes from the border pass)
+                rc = jp_conv_small_fwd(dy, Cout, 0, nullptr, 0, 0, nullptr, 0, 0, wf, nullptr, dx, N, H, W, C, JP_ACT_NONE, 0, st, accs[i]);
+                break;
+            case DG_P9:
+            case DG_ROW_TILE:
+            case DG_TAP: main_pass(s.kind, a, wfr, coff / bmt, b, e, C, g, dy, st); break;
+            case DG_P9SD: {     // its pack sits behind the P9 one
                 const float* xam = JP_NS == 2 ? jp_amax_of(dy, (long)N * Cout * H * W, st) : nullptr;
                 jp_prof_before(p9sd_tag<DgradEpi>(), JP_NPROD * 2.0 * C * (double)np2 * 16.0 * Cp, st);
                 dim3 grid(N * (h2 / 4) * (w2 / 32), jp_cdiv(C, 128), 1);
                 hipLaunchKernelGGL((jp_igemm_p9sd_kernel<DgradEpi>), grid, dim3(256), 0, st, reinterpret_cast<const unsigned*>(wsd), dy, e,
                                    C, Cout, Cp / 16, h2, w2, xam);
                 jp_prof_after(st);
-            } else
-            launch_auto(a, bu, e, C, (int)np2, KpU, 1, KpU, st);
-            const int Nb = N * (2 * w2 + 2 * h2);
-            DgradUPBorderB bb{dy, Nb, h2, w2, Cout};
-            DgradEdgeEpi be{dx, C, h2, w2, Nb, 0};
-            const long btiles = (long)jp_cdiv(C, C <= 64 ? 64 : 128) * jp_cdiv(Nb, C <= 64 ? 256 : 128);
-            // 16 slots x Cout: a long K loop of branchy gathers on a few dozen tiles -- up to 4 K slices (atomic epilogue)
-            const int bsp = (int)std::max<long>(border_splits(btiles, KpU / KC), std::min<long>(4, jp_cdiv(256, btiles)));
-            const int bkps = jp_cdiv(jp_cdiv(KpU, bsp), KC) * KC;
-            be.split = jp_cdiv(KpU, bkps) > 1;
-            if (be.split && split_ws) {
-                // K slices to scratch, then one fixed-order fold into dx (round 6: the slices met in float atomics -- run-dependent last
-                // bits in the gradient of the upsampled segment, which the whole coarser decoder level inherits)
-                const int nsl = std::min(jp_cdiv(KpU, bkps), 8);
-                const int wkps = jp_cdiv(jp_cdiv(KpU, nsl), KC) * KC, ns2 = jp_cdiv(KpU, wkps);
-                WgradEpiWS es{split_ws, C, Nb};
-                launch_auto(a, bb, es, C, Nb, KpU, ns2, wkps, st);
-                const long total = (long)C * Nb;
-                hipLaunchKernelGGL(edge_add_kernel, dim3((int)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, split_ws, dx, C,
-                                   Nb, h2, w2, ns2);
-            } else
-            launch_auto(a, bb, be, C, Nb, KpU, jp_cdiv(KpU, bkps), bkps, st);
+            } break;
+            case DG_UP_TAP: launch_auto(a, DgradUPB{dy, (int)np2, h2, w2, Cout}, e, C, (int)np2, KpU, 1, KpU, st); break;
+            default:
+                jp_set_last_error("conv2d_dgrad_src3: internal: not a kind of dgrad_src3_route");
+                rc = JP_EBADARG;
+                break;
         }
-        coff += C;
+        if (rc) return rc;
+        if (s.up) {
+            edge_pass(a, dy, dx, C, g, s.ring, split_ws, st);
+        } else {
+            border_pass(a, dy, dx, C, g, s.ring, split_ws, st);
+            if (i == 0 && amax_dx0_done) *amax_dx0_done = ax.out_taken ? 1 : 0;
+        }
     }
+    return JP_OK;
+}
+
+// split_ws: optional scratch of jp_conv2d_dgrad_src3_split_floats floats for the ring passes (NULL: read-modify-write epilogue)
+extern "C" int jp_conv2d_dgrad_src3(const float* dy, const float* w, float* dx0, int c0, int up0, int acc0, float* dx1,
+                                    int c1, int up1, int acc1, float* dx2, int c2, int up2, int acc2, int N, int H, int W,
+                                    int Cout, int KH, int stride, int pad, int pad_mode, float* ws, int ws_state,
+                                    float* split_ws, const float* amax_dy, float* amax_dx0, int* amax_dx0_done, float* amax_ws,
+                                    void* stream) {
+    if (amax_dx0_done) *amax_dx0_done = 0;
+    JP_CHECK_ARG(dy && w, "conv2d_dgrad_src3: null pointer");
+    float* const dxs[3] = {dx0, dx1, dx2};
+    const int cs[3] = {c0, c1, c2}, us[3] = {up0, up1, up2}, accs[3] = {acc0, acc1, acc2};
+    const bool want[3] = {dx0 != nullptr, dx1 != nullptr, dx2 != nullptr};
+    const DgradGeom g = dgrad_geom(N, c0 + c1 + c2, H, W, Cout, KH, stride, pad, pad_mode, ws != nullptr, split_ws != nullptr);
+    const Src3Route r = dgrad_src3_route(g, cs, us, want);
+    JP_CHECK_ARG(r.up_head || ws != nullptr, "conv2d_dgrad_src3: null scratch");
+    JP_CHECK_ARG(r.up_head || r.segments, "conv2d_dgrad_src3: shape not supported (check jp_conv2d_dgrad_src3_ok)");
+    JP_CHECK_ARG(r.up_head || JP_NS != 2 || amax_ws || amax_dy, "conv2d_dgrad_src3"": every operand magnitude (amax_*) or amax_ws (jp_conv2d_amax_ws_floats floats of scratch) must be given");
+    JpAmaxCtx ax;
+    ax.know(dy, amax_dy);
+    ax.ws = amax_ws;
+    const JpCall st((hipStream_t)stream, &ax);
+    int rc = JP_OK;
+    if (!r.up_head) rc = run_segments(g, r, dy, w, dxs, accs, ws, ws_state, split_ws, amax_dx0, amax_dx0_done, ax, st);
+    else if (dx0) rc = jp_up_head_dgrad(dy, w, dx0, N, c0, H / 2, W / 2, acc0, st);
+    if (rc) return rc;
     JP_LAUNCH_CHECK();
 }
+
